@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of the MobileNetV2-DeepLabV3+ (ASPP 6/12/18 + decoder) training step,
 513x513x3 synthetic batches, 21 classes, OS=16, fp32, per-GPU batch 16 (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`,
    one rank per GPU over RCCL; weak scaling: per-GPU batch fixed)
 
@@ -54,7 +54,44 @@ def parse():
                          '0: fp32-input MFMA everywhere; default: DL3P_SPLIT_GEMM or 1')
     ap.add_argument('--no-other-configs', action='store_true',
                     help='skip the short runs of BASELINE.json configs[2..4] behind the headline region')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (its loss and the updated weights) as '
+                         'DIR/<name>.npy (rank 0; at most 64 MB, larger weight sets as a fixed seeded sample)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(d, loss, weights, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the train step's result as a caller of it receives it -- the data loss (float64) and every weight
+    after the SGD update (float32, one file per parameter, '/' in the Keras name -> '.').  When the weights do not fit the
+    budget, each tensor is cut to the same fraction of its elements at positions drawn from a generator seeded by its name,
+    so that two runs (and two builds) sample the same elements.  -> {file name: shape}"""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    loss = np.asarray([loss], dtype=np.float64)
+    total = sum(int(np.asarray(w).size) * 4 for w in weights.values())
+    room = budget - loss.nbytes - 128 * (len(weights) + 1)       # (npy headers)
+    frac = 1.0 if total <= room else room / total
+    written = {}
+    np.save(os.path.join(d, 'loss.npy'), loss)
+    written['loss.npy'] = loss.shape
+    for name in sorted(weights):
+        a = np.asarray(weights[name], dtype=np.float32)
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            k = max(1, int(flat.size * frac))
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.size, k, replace=False))
+            a = flat[idx]
+        f = name.replace('/', '.').replace(':', '.') + '.npy'
+        np.save(os.path.join(d, f), a)
+        written[f] = a.shape
+    return written
 
 
 def head_name(model_type, OS):
@@ -352,6 +389,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     loss = float(ex.loss.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below runs more steps on these weights
+        dumped = dump_outputs(args.dump_outputs, loss, model.get_weights_by_name())
     pw_probe = None
     if want_pw_probe:
         # a few more steps AFTER the timed region with the GEMM launch between event pairs (the launch leaves the hipGraph
@@ -388,6 +429,8 @@ def main():
                        'collectives_per_step': sum(getattr(pl, 'n_collectives', 0) for pl in (ex.fwd, ex.bwd, ex.opt)),
                        'rccl_ranks': (torch.distributed.get_world_size() if (world > 1 and torch.distributed.is_initialized()) else 1)},
         }
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'files': len(dumped)}
         standalone = None
         if not probe and probe_name and dist_mode and args.dtype == 'f32':
             # N > 1: the forward is one graph (collectives captured), so the roofline launch is re-issued on the buffers of

@@ -37,7 +37,9 @@ else:
         r = subprocess.run([sys.executable, __file__, 'child'], env=e, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith('LOSSES')]
         if not line:
-            print(tag, 'FAILED', r.stderr[-2000:]); sys.exit(1)
+            # the error line first: a C++ backtrace after it can fill the tail on its own
+            errs = [l for l in r.stderr.splitlines() if 'rror' in l and not l.lstrip().startswith('frame #')][:5]
+            print(tag, 'FAILED rc=%d' % r.returncode, '\n'.join(errs), r.stderr[-2000:]); sys.exit(1)
         out[tag] = json.loads(line[0][7:])
         print(tag, out[tag])
     assert out['single'] == out['forced_dist'] == out['forced_dist_segmented'], 'trajectories differ'

@@ -127,6 +127,8 @@ def test_bench_gpus_flag_spawns_the_ranks(monkeypatch):
         seen['cmd'], seen['env'] = cmd, kw.get('env', {})
         return R()
     monkeypatch.setattr(subprocess, 'run', fake_run)
+    # main() sets HSA_ENABLE_IPC_MODE_LEGACY in os.environ: on a copy, so that it does not reach the later tests' processes
+    monkeypatch.setattr(os, 'environ', os.environ.copy())
     monkeypatch.setattr('sys.argv', ['bench.py', '--gpus', '4', '--steps', '3', '--warmup', '1'])
     monkeypatch.delenv('WORLD_SIZE', raising=False)
     with pytest.raises(SystemExit) as e:
