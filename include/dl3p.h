@@ -277,6 +277,26 @@ int dl3p_stem_conv_bwd_weight(const float* x, int ldx, const float* dy, int lddy
  *   bwd_weight: gw [k*k*Cin][Cout] (+ gb [Cout] = column sums of dy, or NULL), deterministic slab reduction in
  *               `workspace`. */
 int dl3p_conv2d_gemm_supported(int Cin, int Cout, int k, int stride);
+/* Narrow-output dense convs (csrc/conv_narrow.hip; PeleeNet's dense-layer 3x3 convs, deeplabv3p_peleenet.py:73-83): k = 3,
+ * stride 1, rate 1, 'same' (Ho = H, Wo = W), Cin % 4 == 0 and <= 64, Cout in {4, 8, 16, 32}, no bias.  Direct packed-FMA
+ * kernels with the input tile and its 1-pixel halo staged in LDS.  w: the HWIO kernel [3][3][Cin][Cout] as stored.
+ *   fwd:        prologue on x, y may be a channel slice; stat_partials / rows_out as for dl3p_conv2d_gemm_fwd (at most 1024 rows).
+ *   bwd_data:   gx (+)= d/d(act(x)), every input pixel written.
+ *   bwd_weight: gw [3*3*Cin][Cout]; _slabs leaves *rows_out slabs of 9*Cin*Cout floats in `workspace` for
+ *               dl3p_reduce_rows(_batched); deterministic, no atomics. */
+int dl3p_conv_narrow_supported(int Cin, int Cout, int k, int stride, int rate);
+int dl3p_conv_narrow_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
+                         const float* w, float* y, int ldy, float* stat_partials, int* rows_out, int N, int H, int W,
+                         int Cin, int Cout, void* stream);
+int dl3p_conv_narrow_bwd_data(const float* dy, int lddy, const float* w, float* gx, int ldgx, int accumulate,
+                              int N, int H, int W, int Cin, int Cout, void* stream);
+size_t dl3p_conv_narrow_bwd_weight_workspace(int N, int H, int W, int Cin, int Cout);
+int dl3p_conv_narrow_bwd_weight_slabs(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
+                                      const float* dy, int lddy, float* workspace, size_t workspace_bytes, int* rows_out,
+                                      int N, int H, int W, int Cin, int Cout, void* stream);
+int dl3p_conv_narrow_bwd_weight(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
+                                const float* dy, int lddy, float* gw, float* workspace, size_t workspace_bytes,
+                                int N, int H, int W, int Cin, int Cout, void* stream);
 int dl3p_conv2d_gemm_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
                          const float* wt, const float* bias, float* y, int ldy, float* stat_partials, int* rows_out,
                          int N, int H, int W, int Cin, int Cout, int k, int stride, int rate, int pad_t, int pad_l,
@@ -445,6 +465,14 @@ int dl3p_maxpool2d_fwd(const float* x, int ldx, const float* in_scale, const flo
 int dl3p_maxpool2d_bwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
                        const float* dy, int lddy, const uint8_t* argmax, float* gx, int ldgx, int accumulate,
                        int N, int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo, void* stream);
+/* AveragePooling2D((k,k), strides, 'valid') (deeplabv3p_peleenet.py:249-253, PeleeNet's transitions: k = stride = 2), k and
+ * stride in 1..3, Ho = (H - k) / stride + 1 (floor).  x may carry a prologue; y may be a channel slice (ldy != C).  Backward:
+ * gx (+)= the mean's transpose w.r.t. the activated input, gather form (one thread per input pixel x 4 channels, deterministic);
+ * rows / columns no window covers get zero.  The backward needs no x. */
+int dl3p_avgpool2d_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
+                       float* y, int ldy, int N, int H, int W, int C, int k, int stride, int Ho, int Wo, void* stream);
+int dl3p_avgpool2d_bwd(const float* dy, int lddy, float* gx, int ldgx, int accumulate, int N, int H, int W, int C, int k,
+                       int stride, int Ho, int Wo, void* stream);
 /* tf.image.resize(method='bilinear'), half-pixel centres, no antialias (layers.py:48-60):
  * src=(o+0.5)*in/out-0.5; lo=max(floor(src),0); hi=min(ceil(src),in-1); t=src-floor(src). */
 int dl3p_resize_bilinear_fwd(const float* x, int ldx, float* y, int ldy,
@@ -662,6 +690,11 @@ int dl3p_maxpool2d_fwd_bf16(const void* x, int ldx, const float* in_scale, const
                             int pad_l, int Ho, int Wo, void* stream);
 int dl3p_maxpool2d_bwd_bf16(const void* dy, int lddy, const uint8_t* argmax, void* gx, int ldgx, int accumulate, int N,
                             int H, int W, int C, int k, int stride, int pad_t, int pad_l, int Ho, int Wo, void* stream);
+/* bf16 twins of dl3p_avgpool2d_fwd / dl3p_avgpool2d_bwd: bf16 tensors, fp32 sums, one rounding at the store */
+int dl3p_avgpool2d_fwd_bf16(const void* x, int ldx, const float* in_scale, const float* in_shift, int in_act, void* y,
+                            int ldy, int N, int H, int W, int C, int k, int stride, int Ho, int Wo, void* stream);
+int dl3p_avgpool2d_bwd_bf16(const void* dy, int lddy, void* gx, int ldgx, int accumulate, int N, int H, int W, int C,
+                            int k, int stride, int Ho, int Wo, void* stream);
 int dl3p_bn_bwd_reduce_bf16(const void* g, int ldg, const void* z, int ldz, const float* scale, const float* shift,
                             int act, const float* save_mean, const float* save_invstd,
                             float* partials, int* rows_out, int M, int C, void* stream);

@@ -799,6 +799,52 @@ __global__ __launch_bounds__(256) void maxpool_bwd_b(MaxPoolB p) {
     st4(o, g);
   }
 }
+// AveragePooling2D(k, strides, 'valid') (deeplabv3p_peleenet.py:249-253): the bf16 twins of avgpool_fwd_kernel /
+// avgpool_bwd_kernel (pool.hip).  The prologue is rounded to bf16 like every consumer-side prologue of this path, the k*k taps
+// are summed in fp32 in (ky, kx) order, one rounding at the store.
+__global__ __launch_bounds__(256) void avgpool_fwd_b(MaxPoolB p) {
+  const int c4s = p.C / 4;
+  const float area = (float)(p.k * p.k);
+  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
+    const int c = (int)(s % c4s) * 4;
+    long long r = s / c4s;
+    const int ox = (int)(r % p.Wo); r /= p.Wo;
+    const int oy = (int)(r % p.Ho);
+    const int n = (int)(r / p.Ho);
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = zero4();
+    if (p.scale) { sc = ld4(p.scale + c); sh = ld4(p.shift + c); }
+    const bf16* img = p.x + (size_t)n * p.H * p.W * p.ldx;
+    float4 m = zero4();
+    for (int ky = 0; ky < p.k; ++ky)
+      for (int kx = 0; kx < p.k; ++kx) {
+        float4 v = ld4(img + ((size_t)(oy * p.stride + ky) * p.W + ox * p.stride + kx) * p.ldx + c);
+        if (p.scale || p.act != DL3P_ACT_NONE) v = bf16_round4(act_apply4(p.scale ? fma4(v, sc, sh) : v, p.act));
+        m = add4(m, v);
+      }
+    st4(p.y + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.ldy + c, make_float4(m.x / area, m.y / area, m.z / area, m.w / area));
+  }
+}
+// gather form: an input pixel sums dy over the windows that contain it (none: zero)
+__global__ __launch_bounds__(256) void avgpool_bwd_b(MaxPoolB p) {
+  const int c4s = p.C / 4;
+  const float area = (float)(p.k * p.k);
+  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
+    const int c = (int)(s % c4s) * 4;
+    long long r = s / c4s;
+    const int ix = (int)(r % p.W); r /= p.W;
+    const int iy = (int)(r % p.H);
+    const int n = (int)(r / p.H);
+    float4 g = zero4();
+    const int oy_hi = min(iy / p.stride, p.Ho - 1), ox_hi = min(ix / p.stride, p.Wo - 1);
+    for (int oy = oy_hi; oy >= 0 && oy * p.stride + p.k > iy; --oy)
+      for (int ox = ox_hi; ox >= 0 && ox * p.stride + p.k > ix; --ox)
+        g = add4(g, ld4(p.dy + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.lddy + c));
+    g = make_float4(g.x / area, g.y / area, g.z / area, g.w / area);
+    bf16* o = p.y + (((size_t)n * p.H + iy) * p.W + ix) * p.ldy + c;
+    if (p.accumulate) g = add4(g, ld4(o));
+    st4(o, g);
+  }
+}
 inline unsigned pool_grid_b(long long total) {
   long long b = (total + 255) / 256;
   const long long cap = (long long)DL3P_NUM_CUS * 16;
@@ -895,5 +941,36 @@ extern "C" int dl3p_transpose_batch_bf16(const float* src, void* dst, const int*
   DL3P_CHECK_ARG(src && dst && table && n_matrices > 0, "dl3p_transpose_batch_bf16: bad arguments");
   hipLaunchKernelGGL(transpose_batch_b, dim3(n_matrices, 96), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, table);
   DL3P_CHECK_LAUNCH("dl3p_transpose_batch_bf16");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_avgpool2d_fwd_bf16(const void* x, int ldx, const float* in_scale, const float* in_shift, int in_act, void* y,
+                                       int ldy, int N, int H, int W, int C, int k, int stride, int Ho, int Wo, void* stream) {
+  DL3P_CHECK_ARG(x && y && ((uintptr_t)x & 7u) == 0 && ((uintptr_t)y & 7u) == 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C &&
+                 ldy % 4 == 0 && ldy >= C && N > 0 && k >= 1 && k <= 3 && stride >= 1 && stride <= 3 && H >= k && W >= k &&
+                 Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1 && !in_scale == !in_shift &&
+                 (!in_scale || (((uintptr_t)in_scale & 15u) == 0 && ((uintptr_t)in_shift & 15u) == 0)),
+                 "dl3p_avgpool2d_fwd_bf16: bad arguments (scale and shift come together, 16-byte aligned)");
+  MaxPoolB p = {};
+  p.x = (const bf16*)x; p.ldx = ldx; p.scale = in_scale; p.shift = in_shift; p.act = in_act; p.y = (bf16*)y; p.ldy = ldy;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.k = k; p.stride = stride; p.Ho = Ho; p.Wo = Wo;
+  p.total = (long long)N * Ho * Wo * (C / 4);
+  hipLaunchKernelGGL(avgpool_fwd_b, dim3(pool_grid_b(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_avgpool2d_fwd_bf16");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_avgpool2d_bwd_bf16(const void* dy, int lddy, void* gx, int ldgx, int accumulate, int N, int H, int W, int C,
+                                       int k, int stride, int Ho, int Wo, void* stream) {
+  DL3P_CHECK_ARG(dy && gx && ((uintptr_t)dy & 7u) == 0 && ((uintptr_t)gx & 7u) == 0 && C > 0 && C % 4 == 0 && lddy % 4 == 0 &&
+                 lddy >= C && ldgx % 4 == 0 && ldgx >= C && N > 0 && k >= 1 && k <= 3 && stride >= 1 && stride <= 3 &&
+                 H >= k && W >= k && Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1,
+                 "dl3p_avgpool2d_bwd_bf16: bad arguments");
+  MaxPoolB p = {};
+  p.dy = (const bf16*)dy; p.lddy = lddy; p.y = (bf16*)gx; p.ldy = ldgx; p.accumulate = accumulate;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.k = k; p.stride = stride; p.Ho = Ho; p.Wo = Wo;
+  p.total = (long long)N * H * W * (C / 4);
+  hipLaunchKernelGGL(avgpool_bwd_b, dim3(pool_grid_b(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_avgpool2d_bwd_bf16");
   return DL3P_OK;
 }

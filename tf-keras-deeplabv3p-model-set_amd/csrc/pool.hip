@@ -115,6 +115,54 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(PoolParams p) {
   }
 }
 
+// AveragePooling2D(pool_size=k, strides=s, padding='valid') (deeplabv3p_peleenet.py:249-253, k = s = 2): every window lies
+// inside the image (floor-sized output), the mean is the sum of its k*k taps in (ky, kx) order divided by k*k.  The input may
+// carry its producer's BatchNorm + activation as a prologue; the output may be a channel slice (ldy != C).
+__global__ __launch_bounds__(256) void avgpool_fwd_kernel(PoolParams p) {
+  const int c4s = p.C / 4;
+  const float area = (float)(p.k * p.k);
+  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
+    const int c = (int)(s % c4s) * 4;
+    long long r = s / c4s;
+    const int ox = (int)(r % p.Wo); r /= p.Wo;
+    const int oy = (int)(r % p.Ho);
+    const int n = (int)(r / p.Ho);
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = zero4();
+    if (p.scale) { sc = ld4(p.scale + c); sh = ld4(p.shift + c); }
+    const float* img = p.x + (size_t)n * p.H * p.W * p.ldx;
+    float4 m = zero4();
+    for (int ky = 0; ky < p.k; ++ky)
+      for (int kx = 0; kx < p.k; ++kx)
+        m = add4(m, pool_in(p, img, oy * p.stride + ky, ox * p.stride + kx, c, sc, sh));
+    st4(p.y + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.ldy + c, make_float4(m.x / area, m.y / area, m.z / area, m.w / area));
+  }
+}
+
+// gather form (deterministic), one thread per (input pixel, 4 channels): the sum of dy over the windows that contain the
+// pixel, divided by k*k -- the gradient w.r.t. the ACTIVATED input (the producer's BatchNorm backward applies act').  Rows
+// and columns no window covers (H - k not a multiple of the stride) get zero.
+__global__ __launch_bounds__(256) void avgpool_bwd_kernel(PoolParams p) {
+  const int c4s = p.C / 4;
+  const float area = (float)(p.k * p.k);
+  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
+    const int c = (int)(s % c4s) * 4;
+    long long r = s / c4s;
+    const int ix = (int)(r % p.W); r /= p.W;
+    const int iy = (int)(r % p.H);
+    const int n = (int)(r / p.H);
+    float4 g = zero4();
+    // windows oy with oy*stride <= iy < oy*stride + k, 0 <= oy < Ho (same for x)
+    const int oy_hi = min(iy / p.stride, p.Ho - 1), ox_hi = min(ix / p.stride, p.Wo - 1);
+    for (int oy = oy_hi; oy >= 0 && oy * p.stride + p.k > iy; --oy)
+      for (int ox = ox_hi; ox >= 0 && ox * p.stride + p.k > ix; --ox)
+        g = add4(g, ld4(p.dy + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.lddy + c));
+    g = make_float4(g.x / area, g.y / area, g.z / area, g.w / area);
+    float* o = p.y + (((size_t)n * p.H + iy) * p.W + ix) * p.ldy + c;
+    if (p.accumulate) g = add4(g, ld4(o));
+    st4(o, g);
+  }
+}
+
 int check(const char* fn, const void* a, int ld, int C) {
   DL3P_CHECK_ARG(a && aligned16(a) && ld % 4 == 0 && ld >= C, "%s: bad tensor layout (ld=%d, C=%d)", fn, ld, C);
   return DL3P_OK;
@@ -164,5 +212,42 @@ extern "C" int dl3p_maxpool2d_bwd(const float* x, int ldx, const float* in_scale
   p.total = (long long)N * H * W * (C / 4);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(p.total)), dim3(256), 0, (hipStream_t)stream, p);
   DL3P_CHECK_LAUNCH("dl3p_maxpool2d_bwd");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_avgpool2d_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
+                                  float* y, int ldy, int N, int H, int W, int C, int k, int stride, int Ho, int Wo,
+                                  void* stream) {
+  DL3P_CHECK_ARG(C > 0 && C % 4 == 0 && N > 0 && k >= 1 && k <= 3 && stride >= 1 && stride <= 3 && H >= k && W >= k &&
+                 Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1, "dl3p_avgpool2d_fwd: bad dims");
+  DL3P_CHECK_ARG(!in_scale == !in_shift && (!in_scale || (aligned16(in_scale) && aligned16(in_shift))),
+                 "dl3p_avgpool2d_fwd: scale and shift come together, 16-byte aligned");
+  int rc = check("dl3p_avgpool2d_fwd", x, ldx, C);
+  if (rc) return rc;
+  rc = check("dl3p_avgpool2d_fwd", y, ldy, C);
+  if (rc) return rc;
+  PoolParams p = {};
+  p.x = x; p.ldx = ldx; p.scale = in_scale; p.shift = in_shift; p.act = in_act; p.y = y; p.ldy = ldy;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.k = k; p.stride = stride; p.Ho = Ho; p.Wo = Wo;
+  p.total = (long long)N * Ho * Wo * (C / 4);
+  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_avgpool2d_fwd");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_avgpool2d_bwd(const float* dy, int lddy, float* gx, int ldgx, int accumulate, int N, int H, int W,
+                                  int C, int k, int stride, int Ho, int Wo, void* stream) {
+  DL3P_CHECK_ARG(C > 0 && C % 4 == 0 && N > 0 && k >= 1 && k <= 3 && stride >= 1 && stride <= 3 && H >= k && W >= k &&
+                 Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1, "dl3p_avgpool2d_bwd: bad dims");
+  int rc = check("dl3p_avgpool2d_bwd", dy, lddy, C);
+  if (rc) return rc;
+  rc = check("dl3p_avgpool2d_bwd", gx, ldgx, C);
+  if (rc) return rc;
+  PoolParams p = {};
+  p.y = gx; p.ldy = ldgx; p.dy = dy; p.lddy = lddy; p.accumulate = accumulate;
+  p.N = N; p.H = H; p.W = W; p.C = C; p.k = k; p.stride = stride; p.Ho = Ho; p.Wo = Wo;
+  p.total = (long long)N * H * W * (C / 4);
+  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_avgpool2d_bwd");
   return DL3P_OK;
 }

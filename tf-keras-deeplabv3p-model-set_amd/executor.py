@@ -450,7 +450,8 @@ class Executor:
         g, N = self.g, self.N
         self.buf, self.grad = {}, {}
         self._mark_requires_grad()
-        direct_cols = {op.col.id for op in g.ops if op.kind == 'conv_dense' and (self._stem_direct(op) or self._dense_gemm(op))}
+        direct_cols = {op.col.id for op in g.ops if op.kind == 'conv_dense' and (self._stem_direct(op) or self._dense_gemm(op)
+                                                                                  or self._narrow(op))}
         # the data-gradient GEMM of an implicit-GEMM conv reads the kernel as [Cin][k*k*Cout] (rebuilt every step)
         self.dense_wd_sb = {}       # id(op) -> (its three bf16 planes, the one-row job table of the split)
         self.dense_wd = {id(op): torch.zeros(op.k * op.k * op.cin * op.cout, **self.f32) for op in g.ops
@@ -514,6 +515,8 @@ class Executor:
                     ws = max(ws, L.stem_conv_bwd_weight_workspace(N, op.Ho, op.Wo, op.cout))
                 if self._dense_gemm(op):
                     ws = max(ws, L.conv2d_gemm_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout, op.k))
+                if self._narrow(op):
+                    ws = max(ws, L.conv_narrow_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout))
         self.workspace = torch.zeros(ws // 4 + 4, **self.f32) if self.training else None
         # slabs of the split-K forward GEMMs (dl3p_pwconv_fwd_wt_splitk), training and inference
         sk = 0 if self.bf16 else max([L.pwconv_fwd_splitk_workspace(N * op.Ho * op.Wo, op.cin, op.cout)
@@ -711,6 +714,8 @@ class Executor:
             return L.dwconv2d_bwd_weight_workspace(N, op.Ho, op.Wo, op.c, op.k)
         if self._stem_direct(op):
             return L.stem_conv_bwd_weight_workspace(N, op.Ho, op.Wo, op.cout)
+        if self._narrow(op):
+            return L.conv_narrow_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout)
         if self._dense_gemm(op):
             return L.conv2d_gemm_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout, op.k)
         return 0
@@ -732,11 +737,22 @@ class Executor:
         self._wgrad_jobs = jt
         P.k(L.reduce_rows_batched, jt.data_ptr(), mt[0].data_ptr(), len(maps[0]), mt[1].data_ptr(), len(maps[1]))
 
+    def _narrow(self, op):
+        """3x3 stride-1 'same' conv with Cout <= 32 and Cin <= 64 on the fp32 path (PeleeNet's dense layers): the direct
+        kernels of csrc/conv_narrow.hip, with DL3P_NARROW_CONV=1 only.  Off by default: measured slower than the implicit GEMM in
+        every role and at every PeleeNet shape (27.0 against 16.4 ms per 512 x 512 batch-16 step)."""
+        xt = op.x.tensor
+        return bool(op.kind == 'conv_dense' and not self.bf16 and op.b is None and op.Ho == xt.H and op.Wo == xt.W
+                    and op.pad_t == (op.k - 1) // 2 and op.pad_l == (op.k - 1) // 2 and op.cout == op.w.shape[3]
+                    and not self._stem_direct(op)
+                    and self.L.conv_narrow_supported(op.cin, op.cout, op.k, op.stride, op.rate)
+                    and os.environ.get('DL3P_NARROW_CONV', '0') == '1')
+
     def _dense_gemm(self, op):
         """dense conv with Cin % 4 == 0 on the fp32 path: implicit GEMM, the patch operand gathered while the GEMM stages
         its A tile (csrc/pwconv.hip, dl3p_conv2d_gemm_*) -- no im2col matrix, no col2im pass"""
         xt = op.x.tensor
-        return (not self.bf16 and not self._stem_direct(op)
+        return (not self.bf16 and not self._stem_direct(op) and not self._narrow(op)
                 and bool(self.L.conv2d_gemm_supported(op.cin, op.cout, op.k, op.stride))
                 # the gather decodes row indices in 24-bit arithmetic; larger tensors keep the im2col route
                 and self.N * xt.H * xt.W < (1 << 24) and self.N * op.Ho * op.Wo < (1 << 24))
@@ -764,7 +780,7 @@ class Executor:
                 setrg(op.z, op.layer.trainable)
             elif k == 'materialize':
                 setrg(op.out, rg(op.x) or (op.r is not None and rg(op.r)))
-            elif k in ('gap', 'resize', 'broadcast', 'maxpool'):
+            elif k in ('gap', 'resize', 'broadcast', 'maxpool', 'avgpool'):
                 setrg(op.out, rg(op.x))
             elif k == 'se_mul':
                 setrg(op.out, rg(op.x) or rg(op.s))
@@ -882,6 +898,9 @@ class Executor:
                 elif self._stem_direct(op):
                     P.k(L.stem_conv_fwd, xp, ldx, st.ptr(op.w), self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N,
                         xt.H, xt.W, op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo, tag=op.name)
+                elif self._narrow(op):
+                    P.k(L.conv_narrow_fwd, xp, ldx, sp, hp, act, st.ptr(op.w), self.tptr(op.out), op.out.ld, part,
+                        ctypes.byref(rows), N, xt.H, xt.W, op.cin, op.cout, tag=op.name)
                 elif self._dense_gemm(op) and self._use_sb_dense(op, 1 if part is not None else 0):
                     wsp, pitch = st.sb_ptr(op, True)
                     P.k(L.conv2d_gemm_fwd_sb, xp, ldx, sp, hp, act, wsp, pitch, st.ptr(op.b) if op.b else None,
@@ -925,6 +944,11 @@ class Executor:
                 P.k(L.maxpool2d_fwd_bf16 if self.bf16 else L.maxpool2d_fwd, xp, ldx, sp, hp, act, self.tptr(t), t.ld,
                     None if arg is None else arg.data_ptr(), N,
                     xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
+            elif k == 'avgpool':
+                xp, ldx, sp, hp, act = self.vargs(op.x)
+                xt, t = op.x.tensor, op.out
+                P.k(L.avgpool2d_fwd_bf16 if self.bf16 else L.avgpool2d_fwd, xp, ldx, sp, hp, act, self.tptr(t), t.ld, N,
+                    xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
             elif k == 'se_mul':
                 xp, ldx, sp, hp, act = self.vargs(op.x)
                 s_ptr, lds, _, _, sact = self.vargs(op.s)
@@ -1300,6 +1324,9 @@ class Executor:
                     elif self._stem_direct(op):
                         wgrad_slabs(L.stem_conv_bwd_weight_slabs, 28 * op.cout, gw, nb, (xp, ldx, dz, lddz),
                                     (N, xt.H, xt.W, op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo))
+                    elif self._narrow(op):
+                        wgrad_slabs(L.conv_narrow_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, gw, nb,
+                                    (xp, ldx, sp, hp, act, dz, lddz), (N, xt.H, xt.W, op.cin, op.cout))
                     else:
                         wgrad_slabs(L.conv2d_gemm_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, gw, nb,
                                     (xp, ldx, sp, hp, act, dz, lddz),
@@ -1317,6 +1344,9 @@ class Executor:
                     elif self._stem_direct(op):
                         wgrad(L.stem_conv_bwd_weight, xp, ldx, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.cout, op.pad_t,
                               op.pad_l, op.Ho, op.Wo)
+                    elif self._narrow(op):
+                        wgrad(L.conv_narrow_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.cin,
+                              op.cout)
                     elif self._dense_gemm(op):
                         wgrad(L.conv2d_gemm_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, st.ptr(op.b, G) if op.b else None,
                               ws, wsb, N, xt.H, xt.W, op.cin, op.cout, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho,
@@ -1380,6 +1410,8 @@ class Executor:
                     elif k == 'conv_dw':
                         P.k(L.dwconv2d_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, acc, N, xt.H, xt.W, op.c, op.k,
                             op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
+                    elif k == 'conv_dense' and self._narrow(op):
+                        P.k(L.conv_narrow_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, acc, N, xt.H, xt.W, op.cin, op.cout)
                     elif k == 'conv_dense' and self._dense_gemm(op) and op.k > 1:
                         wd = self.dense_wd[id(op)]
                         P.k(L.conv2d_gemm_dgrad_weights, st.ptr(op.w), wd.data_ptr(), op.k, op.cin, op.cout)
@@ -1459,6 +1491,12 @@ class Executor:
                 else:
                     P.k(L.maxpool2d_bwd, xp, ldx, sp, hp, act, self.tptr(out, True), out.ld, self._pool_arg[op].data_ptr(), gp,
                         ldg, self._acc(keyt), N, xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
+            elif k == 'avgpool':
+                # d/d(activated input); the producer's BatchNorm backward applies act' (as behind 'maxpool')
+                xt = op.x.tensor
+                gp, ldg, keyt = self._gbuf(op.x)
+                P.k(L.avgpool2d_bwd_bf16 if self.bf16 else L.avgpool2d_bwd, self.tptr(out, True), out.ld, gp, ldg, self._acc(keyt),
+                    N, xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
             elif k == 'gap':
                 xt = op.x.tensor
                 gp, ldg, keyt = self._gbuf(op.x)

@@ -390,8 +390,9 @@ class GraphBuilder:
         self.ops.append(Op('se_mul', name=out.name, x=x, s=s, out=out))
         return Value(out, klayer=layer)
 
-    def maxpool2d(self, v, k, stride, pad, name=None, pad_name=None):
-        """ZeroPadding2D(pad) + MaxPooling2D((k,k), strides) (reference deeplabv3p_resnet50.py:266-267)"""
+    def maxpool2d(self, v, k, stride, pad, name=None, pad_name=None, out=None):
+        """ZeroPadding2D(pad) + MaxPooling2D((k,k), strides) (reference deeplabv3p_resnet50.py:266-267); `out`: write the result
+        into a Concatenate slice (PeleeNet's stem block, deeplabv3p_peleenet.py:107-109)"""
         H, W, C = v.shape
         pt, pb, pl, pr = pad
         src = v
@@ -399,8 +400,23 @@ class GraphBuilder:
             src = self.add_layer(pad_name, 'ZeroPadding2D', inbound=[v])
         Ho, Wo = (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
         layer = self.add_layer(name, 'MaxPooling2D', (Ho, Wo, C), inbound=[src])
-        out = self.new_tensor(Ho, Wo, C, layer.name)
+        if out is None:
+            out = self.new_tensor(Ho, Wo, C, layer.name)
+        assert (out.H, out.W, out.C) == (Ho, Wo, C), (layer.name, (out.H, out.W, out.C), (Ho, Wo, C))
         self.ops.append(Op('maxpool', name=layer.name, x=v, out=out, k=k, stride=stride, pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo))
+        return Value(out, klayer=layer)
+
+    def avgpool2d(self, v, k, stride, name=None, out=None):
+        """AveragePooling2D(pool_size=k, strides=stride, padding='valid') (reference deeplabv3p_peleenet.py:249-253): floor-sized
+        output, mean of k*k taps of the (lazily activated) input.  `out`: write the result into a channel slice (the next dense
+        block's buffer); the result is a materialised tensor."""
+        H, W, C = v.shape
+        Ho, Wo = (H - k) // stride + 1, (W - k) // stride + 1
+        layer = self.add_layer(name, 'AveragePooling2D', (Ho, Wo, C), inbound=[v])
+        if out is None:
+            out = self.new_tensor(Ho, Wo, C, layer.name)
+        assert (out.H, out.W, out.C) == (Ho, Wo, C), (layer.name, (out.H, out.W, out.C), (Ho, Wo, C))
+        self.ops.append(Op('avgpool', name=layer.name, x=v, out=out, k=k, stride=stride, Ho=Ho, Wo=Wo))
         return Value(out, klayer=layer)
 
     def global_avgpool(self, v, name=None, kind='AveragePooling2D'):

@@ -46,6 +46,12 @@ def _register_optional():
         deeplab_model_map['resnet50'] = Deeplabv3pResNet50
     except ImportError:
         pass
+    try:
+        from .peleenet import Deeplabv3pPeleeNet, Deeplabv3pLitePeleeNet
+        deeplab_model_map['peleenet'] = Deeplabv3pPeleeNet
+        deeplab_model_map['peleenet_lite'] = Deeplabv3pLitePeleeNet
+    except ImportError:
+        pass
 
 
 _register_optional()

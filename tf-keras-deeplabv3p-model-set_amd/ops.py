@@ -445,6 +445,68 @@ def maxpool2d_bwd(x, dy, k, stride, pad, in_scale=None, in_shift=None, in_act=AC
     return gx
 
 
+def conv_narrow_fwd(x, w, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None, stats=False):
+    """3x3 stride-1 'same' conv, Cout <= 32 (csrc/conv_narrow.hip): x (N,H,W,Cin), w (3,3,Cin,Cout) -> y (N,H,W,Cout)
+    [, the statistics partial rows (rows, 2, Cout) when stats]"""
+    N, H, W, Cin = x.shape
+    Cout = w.shape[-1]
+    y = out if out is not None else torch.empty((N, H, W, Cout), dtype=torch.float32, device=x.device)
+    part = torch.zeros((1024, 2, Cout), dtype=torch.float32, device=x.device) if stats else None
+    rows = ctypes.c_int(0)
+    xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
+    lib().conv_narrow_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(w.contiguous()), yp, ldy, _p(part),
+                          ctypes.byref(rows), N, H, W, Cin, Cout, _stream())
+    return (y, part[:rows.value]) if stats else y
+
+
+def conv_narrow_bwd_data(dy, w, out=None, accumulate=False):
+    """d/d(act(x)) of conv_narrow_fwd"""
+    N, H, W, Cout = dy.shape
+    Cin = w.shape[2]
+    gx = out if out is not None else torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy.device)
+    dp, ldd = _pl(dy)
+    gp, ldg = _pl(gx)
+    lib().conv_narrow_bwd_data(dp, ldd, _p(w.contiguous()), gp, ldg, int(accumulate), N, H, W, Cin, Cout, _stream())
+    return gx
+
+
+def conv_narrow_bwd_weight(x, dy, in_scale=None, in_shift=None, in_act=ACT_NONE):
+    """gw (3,3,Cin,Cout) of conv_narrow_fwd (slabs + the deterministic row reduction)"""
+    N, H, W, Cin = x.shape
+    Cout = dy.shape[-1]
+    gw = torch.empty((3, 3, Cin, Cout), dtype=torch.float32, device=x.device)
+    nbytes = lib().conv_narrow_bwd_weight_workspace(N, H, W, Cin, Cout)
+    ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=x.device)
+    xp, ldx = _pl(x)
+    dp, ldd = _pl(dy)
+    lib().conv_narrow_bwd_weight(xp, ldx, _p(in_scale), _p(in_shift), in_act, dp, ldd, _p(gw), _p(ws), nbytes, N, H, W, Cin,
+                                 Cout, _stream())
+    return gw
+
+
+def avgpool2d_fwd(x, k, stride, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None):
+    """x (N,H,W,C) -> AveragePooling2D((k,k), strides, 'valid'); `out` may be a channel slice of a wider buffer"""
+    N, H, W, C = x.shape
+    Ho, Wo = (H - k) // stride + 1, (W - k) // stride + 1
+    y = out if out is not None else torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
+    lib().avgpool2d_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, yp, ldy, N, H, W, C, k, stride, Ho, Wo, _stream())
+    return y
+
+
+def avgpool2d_bwd(dy, x_shape, k, stride, out=None, accumulate=False):
+    """d/d(activated input) of AveragePooling2D; `out` (+)= it"""
+    N, H, W, C = x_shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    gx = out if out is not None else torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    dp, ldd = _pl(dy)
+    gp, ldg = _pl(gx)
+    lib().avgpool2d_bwd(dp, ldd, gp, ldg, int(accumulate), N, H, W, C, k, stride, Ho, Wo, _stream())
+    return gx
+
+
 def resize_bilinear_fwd(x, H, W, out=None):
     N, h, w, C = x.shape
     y = out if out is not None else torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
@@ -1017,6 +1079,26 @@ def maxpool2d_bwd_bf16(dy, argmax, x_shape, k, stride, pad, out=None, accumulate
     dp, ldd, _ = _plb(dy)
     gp, ldg, _ = _plb(gx)
     lib().maxpool2d_bwd_bf16(dp, ldd, _p(argmax), gp, ldg, int(accumulate), N, H, W, C, k, stride, pt, pl, Ho, Wo, _stream())
+    return gx
+
+
+def avgpool2d_fwd_bf16(x, k, stride, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None):
+    N, H, W, C = x.shape
+    Ho, Wo = (H - k) // stride + 1, (W - k) // stride + 1
+    y = out if out is not None else torch.empty((N, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
+    xp, ldx, _ = _plb(x)
+    yp, ldy, _ = _plb(y)
+    lib().avgpool2d_fwd_bf16(xp, ldx, _p(in_scale), _p(in_shift), in_act, yp, ldy, N, H, W, C, k, stride, Ho, Wo, _stream())
+    return y
+
+
+def avgpool2d_bwd_bf16(dy, x_shape, k, stride, out=None, accumulate=False):
+    N, H, W, C = x_shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    gx = out if out is not None else torch.empty(x_shape, dtype=torch.bfloat16, device=dy.device)
+    dp, ldd, _ = _plb(dy)
+    gp, ldg, _ = _plb(gx)
+    lib().avgpool2d_bwd_bf16(dp, ldd, gp, ldg, int(accumulate), N, H, W, C, k, stride, Ho, Wo, _stream())
     return gx
 
 
