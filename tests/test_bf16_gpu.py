@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import load_pkg
+from layer_walk import _act64, _taps
 from oracle import np_ops as O
 
 pytestmark = pytest.mark.gpu
@@ -517,28 +518,6 @@ def test_bf16_full_size_properties():
 # round 4: the layer-local check AT 1024 x 2048.  The NumPy oracle needs many minutes for one configs[4]
 # image, so the reference here is float64 torch ON THE DEVICE (matmul / shifted multiply-adds -- no kernel of this repo, no conv
 # library), layer by layer from the DEVICE's own stored tensors, with bf16 rounding at the points the policy defines.
-def _act64(u, act):
-    O_ = load_pkg('ops')
-    if act == O_.ACT_NONE:
-        return u
-    if act == O_.ACT_RELU:
-        return u.clamp_min(0)
-    if act == O_.ACT_RELU6:
-        return u.clamp(0, 6)
-    hs = (u + 3).clamp(0, 6) / 6
-    return hs if act == O_.ACT_HSIGMOID else u * hs
-
-
-def _taps(a, k, stride, rate, pad_t, pad_l, Ho, Wo):
-    """the k x k shifted, strided views of a zero-padded (N, H, W, C) tensor: [(ky, kx, view (N, Ho, Wo, C))]"""
-    N, H, W, C = a.shape
-    need_h, need_w = (Ho - 1) * stride + (k - 1) * rate + 1, (Wo - 1) * stride + (k - 1) * rate + 1
-    ap = torch.nn.functional.pad(a, (0, 0, pad_l, max(0, need_w - W - pad_l), pad_t, max(0, need_h - H - pad_t)))
-    for ky in range(k):
-        for kx in range(k):
-            yield ky, kx, ap[:, ky * rate: ky * rate + (Ho - 1) * stride + 1: stride, kx * rate: kx * rate + (Wo - 1) * stride + 1: stride, :]
-
-
 def test_bf16_every_layer_at_1024x2048_matches_float64_on_the_devices_own_inputs(monkeypatch):
     """BASELINE configs[4] at ITS size (MobileNetV3-Large + ASPP + decoder, 1024 x 2048, 19 classes, batch 1, bf16): every conv /
     depthwise / dense layer's FORWARD output and WEIGHT GRADIENT against float64 computed from the device's own input activations

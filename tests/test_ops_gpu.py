@@ -479,6 +479,90 @@ def test_conv2d_implicit_gemm_split(ops, case):
         L.set_option(b'split_wgrad_tile', -1)
 
 
+def _conv64(a, w, stride, pt, pl, Ho, Wo):
+    """float64 dense conv on the device as k x k shifted slices of the zero-padded input, each times one tap's [Cin, Cout]"""
+    N, H, W, C = a.shape
+    k = w.shape[0]
+    Hp, Wp = (Ho - 1) * stride + k, (Wo - 1) * stride + k
+    ap = torch.zeros((N, Hp, Wp, C), dtype=a.dtype, device=a.device)
+    h, ww = min(H, Hp - pt), min(W, Wp - pl)
+    ap[:, pt:pt + h, pl:pl + ww] = a[:, :h, :ww]
+    y = 0
+    for ky in range(k):
+        for kx in range(k):
+            y = y + ap[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride] @ w[ky, kx]
+    return y
+
+
+# the PeleeNet dense layers' 3x3 convs at a 512 x 512, batch-16 step (block 1: 128 x 128, Cin = inter_channel 16 / 32 / 64 of the
+# blocks, Cout 16 into a 16-channel slice of the block buffer) and stem2b (3x3 stride 2, 16 -> 32 into channels [32, 64) of the
+# 64-wide stem concat): (N, H, W, Cin, Cout, stride, input buffer width, output buffer width, output offset)
+PELEE_GEMM = [(16, 128, 128, 16, 16, 1, 128, 128, 48), (16, 128, 128, 32, 16, 1, 128, 128, 112), (16, 128, 128, 64, 16, 1, 128, 128, 64),
+              (16, 256, 256, 16, 32, 2, 16, 64, 32)]
+
+
+@pytest.mark.parametrize('case', PELEE_GEMM, ids=lambda c: '%dx%d_%d_to_%d_s%d' % (c[1], c[2], c[3], c[4], c[5]))
+@pytest.mark.parametrize('split', [False, True], ids=['fp32', 'split'])
+def test_conv2d_implicit_gemm_peleenet_geometry(ops, case, split):
+    """the default route of PeleeNet's dense-layer convs (DL3P_NARROW_CONV=0) at production length with the production dispatch:
+    x a prefix view of a 128-wide block buffer, the output written into a 16-channel slice at a nonzero offset, dy a slice of the
+    block's gradient buffer, the data gradient accumulated into a prefix of a wider gradient buffer; fp32 kernels and the split
+    route wherever conv2d_gemm_sb_supported serves the launch; float64 on the device"""
+    N, H, W, Cin, Cout, s, ldx, ldy, off = case
+    L = ops.lib()
+    L.set_option(b'pw_small_min_rows', -1)
+    if split:
+        L.set_option(b'conv_sb', 2)
+    try:
+        Ho, Wo, pt, pl = ops.conv_geometry(H, W, 3, s, 1, 'same')
+        M = N * Ho * Wo
+        if split:
+            assert L.conv2d_gemm_sb_supported(1, M, 9 * Cin, Cout) and L.conv2d_gemm_sb_supported(2, N * H * W, 9 * Cout, Cin)
+        g = torch.Generator(device=DEV)
+        g.manual_seed(Cin * 7 + Cout + s)
+        xbuf = torch.randn((N, H, W, ldx), device=DEV, generator=g) * 30.0         # (large values beside the view)
+        x = xbuf[..., :Cin]
+        x.copy_(torch.randn((N, H, W, Cin), device=DEV, generator=g))
+        w = torch.randn((3, 3, Cin, Cout), device=DEV, generator=g) / (9 * Cin) ** 0.5
+        sc = torch.rand(Cin, device=DEV, generator=g) + 0.5
+        sh = torch.randn(Cin, device=DEV, generator=g) * 0.3
+        a64 = torch.addcmul(sh, x, sc).clamp_min(0.0).double().requires_grad_(True)    # the device's fp32 prologue, then float64
+        w64 = w.double().requires_grad_(True)
+        y64 = _conv64(a64, w64, s, pt, pl, Ho, Wo)
+        ybuf = torch.full((N, Ho, Wo, ldy), 3.0, device=DEV)
+        fwd = ops.conv2d_gemm_fwd_sb if split else ops.conv2d_gemm_fwd
+        part = ops.new_partials(Cout, DEV)
+        _, rows = fwd(x, w, s, 1, 'same', sc, sh, ops.ACT_RELU, partials=part, out=ybuf[..., off:off + Cout])
+        ref = y64.detach()
+        scale = float(ref.abs().max())
+        err = float((ybuf[..., off:off + Cout].double() - ref).abs().max())
+        assert err < 3e-5 * scale, (err, scale)
+        assert bool((ybuf[..., :off] == 3.0).all()) and bool((ybuf[..., off + Cout:] == 3.0).all())
+        ps = part[:rows * 2 * Cout].reshape(rows, 2, Cout).double().sum(0)
+        r2 = ref.reshape(-1, Cout)
+        assert bool(((ps[0] - r2.sum(0)).abs() <= 1e-5 * r2.abs().sum(0) + 1e-6 * scale).all())
+        assert bool(((ps[1] - (r2 ** 2).sum(0)).abs() <= 1e-5 * (r2 ** 2).sum(0)).all())
+        # gradients: dy the slice [off, off + Cout) of the block's gradient buffer
+        dybuf = torch.randn((N, Ho, Wo, ldy), device=DEV, generator=g)
+        dy = dybuf[..., off:off + Cout]
+        y64.backward(dy.double())
+        gx_ref, gw_ref = a64.grad, w64.grad
+        gbuf = torch.randn((N, H, W, max(ldx, Cin + 32)), device=DEV, generator=g)
+        base = gbuf.clone()
+        bwd = ops.conv2d_gemm_bwd_data_sb if split else ops.conv2d_gemm_bwd_data
+        bwd(dy, w, (N, H, W, Cin), s, 1, 'same', out=gbuf[..., :Cin], accumulate=True)
+        gscale = float(gx_ref.abs().max())
+        err = float((gbuf[..., :Cin].double() - base[..., :Cin].double() - gx_ref).abs().max())
+        assert err < 3e-5 * max(gscale, float(base[..., :Cin].abs().max())), (err, gscale)
+        assert torch.equal(gbuf[..., Cin:], base[..., Cin:])
+        gw = ops.conv2d_gemm_bwd_weight(x, dy, 3, s, 1, 'same', sc, sh, ops.ACT_RELU)
+        err = float((gw.double() - gw_ref).abs().max())
+        assert err < 1e-4 * float(gw_ref.abs().max()), err
+    finally:
+        L.set_option(b'conv_sb', -1)
+        L.set_option(b'pw_small_min_rows', 64)
+
+
 @pytest.mark.parametrize('case', [(2, 33, 33, 32, 'same'), (1, 32, 48, 16, (0, 1, 0, 1)), (3, 65, 129, 32, 'same'),
                                   (1, 64, 258, 16, 'same'), (2, 17, 263, 32, (0, 1, 0, 1)), (1, 3, 3, 32, 'same'),
                                   (1, 130, 513, 32, 'same')])

@@ -118,8 +118,20 @@ def test_train_step_matches_restatement(mt, OS, narrow, monkeypatch):
     """one SGD step against float64 with the ReLU branch pattern of the float32 run injected (as
     tests/test_model_gpu.py::test_train_step_matches_oracle), with the dense layers' 3x3 convs on either route:
     the direct narrow kernels (DL3P_NARROW_CONV=1, csrc/conv_narrow.hip) or the implicit GEMM (0)"""
+    _train_step_vs_restatement(mt, OS, narrow, 64, 64, monkeypatch)
+
+
+@pytest.mark.parametrize('OS', [8, 16])
+@pytest.mark.parametrize('narrow', ['1', '0'])
+def test_train_step_matches_restatement_ragged(OS, narrow, monkeypatch):
+    """the same step at 72 x 104: block 1 is 18 x 26 (the narrow kernels' 8 x 16 tiles ragged both ways), block 2 9 x 13, the OS-16
+    transition pooling floors 9 x 13 to 4 x 6 (a row and a column no window covers: zero gradient) and the ASPP rates exceed the map"""
+    _train_step_vs_restatement('peleenet', OS, narrow, 72, 104, monkeypatch)
+
+
+def _train_step_vs_restatement(mt, OS, narrow, H, W, monkeypatch):
     monkeypatch.setenv('DL3P_NARROW_CONV', narrow)
-    N, C, H, W = 2, 21, 64, 64
+    N, C = 2, 21
     m, o = _pair(mt, H, W, C, OS)
     m.use_graphs = False
     x, y = _data(N, H, W, C, seed=3)

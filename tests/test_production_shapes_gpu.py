@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import load_pkg
+from layer_walk import _taps
 from oracle import np_ops as O
 from oracle.np_net import OracleModel
 
@@ -353,9 +354,9 @@ def _every_conv_forward_vs_float64_on_device(model_type, H, W, OS, N, C, tol, ex
         assert np.isfinite(loss)
         ex = m._executor(N, True)
         calls = {ep for plan in (ex.fwd,) for (ep, _) in plan.labels}
-        worst, checked = ('', 0.0), 0
+        worst, checked, dense = ('', 0.0), 0, 0
         for op in m.graph.ops:
-            if op.kind not in ('conv_pw', 'conv_dw') or op.out.root.id not in ex.buf or op.x.tensor.root.id not in ex.buf:
+            if op.kind not in ('conv_pw', 'conv_dw', 'conv_dense') or op.out.root.id not in ex.buf or op.x.tensor.root.id not in ex.buf:
                 continue            # (a fused inverted-residual block keeps no expand output; its depthwise conv reads no buffer)
             v = op.x
             a = ex.view(v.tensor).double()
@@ -370,7 +371,16 @@ def _every_conv_forward_vs_float64_on_device(model_type, H, W, OS, N, C, tol, ex
             elif v.act != ops.ACT_NONE:
                 continue
             wk = torch.from_numpy(w0[op.w.name]).to(DEV).double()
-            if op.kind == 'conv_pw':
+            if op.kind == 'conv_dense':
+                a = a[..., :op.cin]
+                ref = 0
+                for ky, kx, s in _taps(a, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo):
+                    ref = ref + s.reshape(-1, op.cin) @ wk[ky, kx]
+                if op.b is not None:
+                    ref = ref + torch.from_numpy(w0[op.b.name]).to(DEV).double()
+                got = ex.view(op.out).double()[..., :wk.shape[-1]]
+                dense += 1
+            elif op.kind == 'conv_pw':
                 real = wk.shape[-1]                  # (the classifier's columns are padded to a multiple of four on the device)
                 ref = a.reshape(-1, op.cin)[:, :wk.shape[-2]] @ wk.reshape(-1, real)
                 if op.b is not None:
@@ -390,7 +400,8 @@ def _every_conv_forward_vs_float64_on_device(model_type, H, W, OS, N, C, tol, ex
             if r > worst[1]:
                 worst = (op.name, r)
             del a, ref, got
-        assert checked >= 20, checked
+        print('%s %dx%d batch %d: %d convs (%d dense) checked, worst %s %.3e' % (model_type, H, W, N, checked, dense, worst[0], worst[1]))
+        assert checked >= 20 and dense >= 1, (checked, dense)
         assert worst[1] < tol, worst
         for k in expect_kernels:
             assert k in calls, (k, sorted(calls))
@@ -403,17 +414,17 @@ def test_headline_batch16_every_conv_forward_matches_float64():
     """BASELINE configs[1] AS THE BENCH RUNS IT (MobileNetV2, 513 x 513, batch 16): 266256-row decoder GEMMs on the pinned-schedule
     kernel, fused 257 x 257 / 129 x 129 blocks, lattice ASPP kernels -- every materialised conv output against float64"""
     n, worst = _every_conv_forward_vs_float64_on_device('mobilenetv2', 513, 513, 16, 16, 21, 2e-5, expect_kernels=('dl3p_pwconv_fwd_sb', 'dl3p_irb_fwd'))
-    assert n >= 40, n
+    assert n >= 62, n                   # (61 pointwise / depthwise + the stem)
 
 
 def test_config3_full_size_every_conv_forward_matches_float64():
     """BASELINE configs[3] at ITS size (Xception, 769 x 769, output stride 8, 19 classes, batch 2): VERDICT r05 weak 5 -- the full size
     had property checks only"""
     n, worst = _every_conv_forward_vs_float64_on_device('xception', 769, 769, 8, 2, 19, 1e-4)
-    assert n >= 100, n
+    assert n >= 147, n                  # (the entry-flow and stem dense convs included)
 
 
 def test_config2_full_size_every_conv_forward_matches_float64():
     """BASELINE configs[2] at its per-GPU shape (Xception, 513 x 513, output stride 16, batch 4: the 4356-row layers)"""
     n, worst = _every_conv_forward_vs_float64_on_device('xception', 513, 513, 16, 4, 21, 1e-4)
-    assert n >= 100, n
+    assert n >= 147, n

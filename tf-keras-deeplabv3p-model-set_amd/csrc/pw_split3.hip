@@ -128,11 +128,21 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_sb3_kernel(GemmParams p) {
       hi[i] = ok ? HI : 0.f;
     }
   };
-  auto load_a = [&](int j) __attribute__((always_inline)) {
-    ra[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rA, arow[j >> 1] + 16 * (j & 1), lkt * (S3_BKT * 4), 0));
+  // the K tail: a quad of k-step lkt at or beyond K (the channels beside a view whose row stride is wider than K, or the next row's)
+  // is requested past the end of the buffer, where the range check returns zeros -- NaN or Inf there must not reach the operand
+  // (x 0 + 0 would keep a NaN, and v_med3 turns it into the lower clamp bound, -Inf without an activation).  Set once per k-step.
+  uint32_t aoff[4];
+  const int kq0 = p.K - ac * 8, kq1 = kq0 - 4;            // the thread's two quads are in [0, K) while lkt * BKT is below these
+  auto k_bounds = [&]() __attribute__((always_inline)) {
+    const int k0 = lkt * S3_BKT;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) aoff[j] = k0 < ((j & 1) ? kq1 : kq0) ? arow[j >> 1] : a_bytes;
   };
-  // prologue coefficients: both vectors in LDS behind the operand stages (copied once, zero from K up: the K tail of the operand
-  // becomes act(0 x + 0) = 0 whatever the buffer holds there), read per step for k-step ckt
+  auto load_a = [&](int j) __attribute__((always_inline)) {
+    ra[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rA, aoff[j] + 16 * (j & 1), lkt * (S3_BKT * 4), 0));
+  };
+  // prologue coefficients: both vectors in LDS behind the operand stages (copied once, zero from K up, where the operand is a
+  // zero-filled load: act(0 x 0 + 0) = 0), read per step for k-step ckt
   float* Cs = reinterpret_cast<float*>(s3_lds + S3_LDS_STAGES);
   const int kpad = p.bsp_pitch;
   if (PRO) {
@@ -218,6 +228,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_sb3_kernel(GemmParams p) {
   {
     __syncthreads();             // (the coefficient vectors)
     row_bounds();
+    k_bounds();
 #pragma unroll
     for (int j = 0; j < 4; ++j) { load_a(j); load_c(j); }
     ckt = 1;
@@ -231,6 +242,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_sb3_kernel(GemmParams p) {
 #pragma unroll
     for (int j = 0; j < 12; ++j) write_b(S0, j);
     ++lkt;                       // (nk >= 8: no wrap here; skt / srem already describe step 1)
+    k_bounds();
 #pragma unroll
     for (int j = 0; j < 4; ++j) { load_a(j); load_c(j); }
     ckt = 2;
@@ -246,6 +258,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_sb3_kernel(GemmParams p) {
     const unsigned short* cur = S0 + P * S3_STAGE;
     unsigned short* nxt = S0 + (P ^ 1) * S3_STAGE;
     row_bounds();
+    k_bounds();
     static_for<96>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       constexpr int kh = g / 48, rem = g % 48, ni = rem / 12, mi = (rem % 12) / 6, pr = rem % 6;
@@ -642,7 +655,7 @@ void launch_sb3_act(const GemmParams& p, bool stats, int grid, hipStream_t st) {
 bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias) {
   if (role < 0 || role > 1 || N != S3_BN || K % 4 || pitch % 64 || pitch < 256 || pitch < K || pitch > 1024 || M < 2 * S3_BM) return false;      // (pitch <= 1024: the coefficient vectors share the LDS)
   if (!(act == DL3P_ACT_NONE || act == DL3P_ACT_RELU || act == DL3P_ACT_RELU6) || accumulate) return false;
-  if (!has_scale && K % 32) return false;                 // (the K tail is zeroed by the out-of-range prologue coefficients)
+  if (!has_scale && K % 32) return false;                 // (no caller needs the unscaled form with a K tail; untested)
   if (role == 1 && bias) return false;                    // (padding rows of the last tile are exact zeros only without a bias)
   return true;
 }

@@ -646,16 +646,18 @@ def conv2d_gemm_supported(Cin, Cout, k, stride):
 
 
 def conv2d_gemm_fwd(x, w, stride=1, rate=1, padding='same', in_scale=None, in_shift=None, in_act=ACT_NONE, bias=None,
-                    partials=None):
-    """dense conv as an implicit GEMM (no im2col matrix): x (N,H,W,Cin), w (k,k,Cin,Cout) -> y (N,Ho,Wo,Cout) [, rows]"""
+                    partials=None, out=None):
+    """dense conv as an implicit GEMM (no im2col matrix): x (N,H,W,Cin), w (k,k,Cin,Cout) -> y (N,Ho,Wo,Cout) [, rows];
+    `out` may be a channel slice of a wider buffer"""
     N, H, W, Cin = x.shape
     k, Cout = w.shape[0], w.shape[-1]
     Ho, Wo, pt, pl = conv_geometry(H, W, k, stride, rate, padding)
     wt = w.reshape(k * k * Cin, Cout).t().contiguous()
-    y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
     xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
     rows = ctypes.c_int(0)
-    lib().conv2d_gemm_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(wt), _p(bias), _p(y), Cout, _p(partials),
+    lib().conv2d_gemm_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(wt), _p(bias), yp, ldy, _p(partials),
                           ctypes.byref(rows), N, H, W, Cin, Cout, k, stride, rate, pt, pl, Ho, Wo, _stream())
     return (y, rows.value) if partials is not None else y
 
@@ -691,16 +693,17 @@ def conv2d_gemm_bwd_weight(x, dy, k, stride=1, rate=1, padding='same', in_scale=
 
 
 def conv2d_gemm_fwd_sb(x, w, stride=1, rate=1, padding='same', in_scale=None, in_shift=None, in_act=ACT_NONE, bias=None,
-                       partials=None):
+                       partials=None, out=None):
     """conv2d_gemm_fwd on the split-bf16 kernel (the kernel operand pre-split here: [3][Cout][pitch >= k k Cin])"""
     N, H, W, Cin = x.shape
     k, Cout = w.shape[0], w.shape[-1]
     Ho, Wo, pt, pl = conv_geometry(H, W, k, stride, rate, padding)
     wsp = split_bf16x3(w.reshape(k * k * Cin, Cout).t().contiguous())
-    y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
     xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
     rows = ctypes.c_int(0)
-    lib().conv2d_gemm_fwd_sb(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(wsp), wsp.shape[2], _p(bias), _p(y), Cout, _p(partials),
+    lib().conv2d_gemm_fwd_sb(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(wsp), wsp.shape[2], _p(bias), yp, ldy, _p(partials),
                              ctypes.byref(rows), N, H, W, Cin, Cout, k, stride, rate, pt, pl, Ho, Wo, _stream())
     return (y, rows.value) if partials is not None else y
 
