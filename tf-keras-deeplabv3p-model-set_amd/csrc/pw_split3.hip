@@ -651,17 +651,30 @@ void launch_sb3_act(const GemmParams& p, bool stats, int grid, hipStream_t st) {
 }
 }  // namespace
 
-// role 0 / 1 (forward without / with statistics), (M, K, N) as launched, pitch = row length of the pre-split kernel planes
-bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias) {
+// The kernels above address rows in uint32 byte offsets for whole tiles: the padding rows of the last tile and, through the prefetch /
+// staging of the next tile, the rows one grid stride past it.  An offset that wraps past 2^32 lands inside the operand, where the range
+// check lets it through (a padding-row store overwrites rows near the start), so every row up to (tiles + grid) x 128 must stay below
+// 2^32 bytes at the widest leading dimension.  ld_max = 0: the leading dimensions are not known yet (planning); the launch asks again.
+static bool s3_offsets_fit(int M, int ld_max) {
+  const unsigned long long tiles = (unsigned long long)ceil_div(M, S3_BM), grid = tiles < DL3P_NUM_CUS ? tiles : DL3P_NUM_CUS;
+  return (tiles + grid) * S3_BM * (unsigned long long)ld_max * 4ull <= (1ull << 32);
+}
+
+// role 0 / 1 (forward without / with statistics), (M, K, N) as launched, pitch = row length of the pre-split kernel planes, ld_max =
+// the wider of the operand's and the output's leading dimensions
+bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias, int ld_max) {
   if (role < 0 || role > 1 || N != S3_BN || K % 4 || pitch % 64 || pitch < 256 || pitch < K || pitch > 1024 || M < 2 * S3_BM) return false;      // (pitch <= 1024: the coefficient vectors share the LDS)
+  if (!s3_offsets_fit(M, ld_max)) return false;
   if (!(act == DL3P_ACT_NONE || act == DL3P_ACT_RELU || act == DL3P_ACT_RELU6) || accumulate) return false;
   if (!has_scale && K % 32) return false;                 // (no caller needs the unscaled form with a K tail; untested)
   if (role == 1 && bias) return false;                    // (padding rows of the last tile are exact zeros only without a bias)
   return true;
 }
-// the data gradient with the folded BatchNorm-backward apply (dl3p_pwconv_bwd_data_sb_apply): 256 output columns, reduction 256 = pitch
-bool dl3p_sb3d_supported(int M, int kout, int nred, int pitch, int f_act, int bb_act, bool bnb, bool accumulate) {
+// the data gradient with the folded BatchNorm-backward apply (dl3p_pwconv_bwd_data_sb_apply): 256 output columns, reduction 256 = pitch;
+// ld_max = the widest leading dimension of g, z_out, dz, gx (and z with the sums)
+bool dl3p_sb3d_supported(int M, int kout, int nred, int pitch, int f_act, int bb_act, bool bnb, bool accumulate, int ld_max) {
   if (kout != S3_BN || nred != S3D_KP || pitch != S3D_KP || M < 2 * S3_BM || accumulate) return false;
+  if (!s3_offsets_fit(M, ld_max)) return false;
   if (!(f_act == DL3P_ACT_NONE || f_act == DL3P_ACT_RELU || f_act == DL3P_ACT_RELU6)) return false;
   if (bnb && !(bb_act == DL3P_ACT_NONE || bb_act == DL3P_ACT_RELU || bb_act == DL3P_ACT_RELU6)) return false;
   return true;

@@ -1230,7 +1230,7 @@ void dl3p_launch_gemm_sbp(const GemmParams& p, bool stats, bool bnb, int nt, int
 // the pinned-schedule form (pw_split3.hip; gemm_plan_sb reports it as wm = 4): forwards onto 256 columns from 65536 rows up whose
 // reduction is 8, 10, 12 ... K-steps long.  dl3p_set_option("sb3", 1) takes it wherever it is supported, 0 never, -1 (default) by
 // the rule -- unless the measured table knows the launch
-bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias);
+bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias, int ld_max);
 int dl3p_sb3_grid(int M);
 bool dl3p_launch_gemm_sb3(GemmParams p, bool stats, int grid, hipStream_t st);
 bool dl3p_launch_gemm_sb3d(GemmParams p, bool bnb, int grid, hipStream_t st);
@@ -1238,7 +1238,7 @@ static thread_local int t_sb3_veto = 0;        // set while a launch whose prolo
 static bool sb3_route(int role, int M, int K, int N) {
   if (g_sb3 < 0) { static const int env = getenv("DL3P_SB3") ? atoi(getenv("DL3P_SB3")) : -1; if (env >= 0) g_sb3 = env; }
   const int pitch = (K + 31) / 32 * 32;
-  if (t_sb3_veto || g_sb3 == 0 || !dl3p_sb3_supported(role, M, K, N, pitch, DL3P_ACT_NONE, true, false, false)) return false;
+  if (t_sb3_veto || g_sb3 == 0 || !dl3p_sb3_supported(role, M, K, N, pitch, DL3P_ACT_NONE, true, false, false, 0)) return false;
   if (g_sb3 == 1) return true;
   if (g_sb_pipe < 0) g_sb_pipe = getenv("DL3P_SB_PIPE") ? atoi(getenv("DL3P_SB_PIPE")) : 0;
   if (g_sb_force_wm != 0 || g_sb_pipe > 0 || g_gemm_force_nt || g_gemm_force_mi || g_sb_rs == 1) return false;       // another form is pinned
@@ -1365,10 +1365,10 @@ extern "C" int dl3p_pwconv_fwd_sb(const float* x, int ldx, const float* in_scale
   p.M = M; p.K = K; p.N = N;
   int nt, gx, gy, mi, wm;
   gemm_plan_sb(stat_partials ? 1 : 0, M, K, N, &nt, &gx, &gy, &p.num_m_tiles, &mi, &wm);
-  if (wm == 4 && !dl3p_sb3_supported(stat_partials ? 1 : 0, M, K, N, pitch, in_act, in_scale != nullptr, false, bias != nullptr)) {
+  if (wm == 4 && !dl3p_sb3_supported(stat_partials ? 1 : 0, M, K, N, pitch, in_act, in_scale != nullptr, false, bias != nullptr, ldx > ldy ? ldx : ldy)) {
     static const bool dbg = getenv("DL3P_SB3_DEBUG") != nullptr;
     if (dbg) fprintf(stderr, "dl3p_pwconv_fwd_sb: pinned form vetoed (M=%d K=%d N=%d pitch=%d act=%d scale=%d bias=%d stats=%d)\n", M, K, N, pitch, in_act, in_scale != nullptr, bias != nullptr, stat_partials != nullptr);
-    t_sb3_veto = 1;          // (an activation / bias / pitch the pinned form does not serve: the tiled kernels take the launch)
+    t_sb3_veto = 1;          // (an activation / bias / pitch / leading dimension the pinned form does not serve: the tiled kernels take it)
     gemm_plan_sb(stat_partials ? 1 : 0, M, K, N, &nt, &gx, &gy, &p.num_m_tiles, &mi, &wm);
     t_sb3_veto = 0;
   }
@@ -1427,8 +1427,8 @@ extern "C" int dl3p_pwconv_bwd_data_sb(const float* dy, int lddy, const void* ws
 }
 
 bool dl3p_sb_rs_fold_supported(int M, int K, int N, int act);
-bool dl3p_sb3d_supported(int M, int kout, int nred, int pitch, int f_act, int bb_act, bool bnb, bool accumulate);
-static bool sb3d_takes(int M, int K, int N, int pitch, int bn_act, int front_act, bool bnb, bool accumulate) {
+bool dl3p_sb3d_supported(int M, int kout, int nred, int pitch, int f_act, int bb_act, bool bnb, bool accumulate, int ld_max);
+static bool sb3d_takes(int M, int K, int N, int pitch, int bn_act, int front_act, bool bnb, bool accumulate, int ld_max) {
   if (g_sb3 < 0) { static const int env = getenv("DL3P_SB3") ? atoi(getenv("DL3P_SB3")) : -1; if (env >= 0) g_sb3 = env; }
   // OPT-IN by rule (DL3P_SB3_DGRAD=1; dl3p_set_option("sb3", 1) takes it wherever it is supported): measured on MI355X the pinned form
   // is 7-12 % faster than the row-stationary kernel without the fused sums (263-300 against 281-340 us on 262144-266256 rows) and
@@ -1436,14 +1436,14 @@ static bool sb3d_takes(int M, int K, int N, int pitch, int bn_act, int front_act
   // 1.09-1.36 GB (g, z, dz, gx and the front layer's z) -- 240-300 us at the 4.5-5 TB/s such kernels reach -- so it is bound by HBM,
   // not by the matrix pipe (scripts/micro/sb3d_bench.py)
   static const int sb3d = getenv("DL3P_SB3_DGRAD") ? atoi(getenv("DL3P_SB3_DGRAD")) : 0;
-  if (g_sb3 == 0 || !dl3p_sb3d_supported(M, K, N, pitch, bn_act, front_act, bnb, accumulate)) return false;
+  if (g_sb3 == 0 || !dl3p_sb3d_supported(M, K, N, pitch, bn_act, front_act, bnb, accumulate, ld_max)) return false;
   return g_sb3 == 1 || (sb3d && M >= 65536);
 }
 extern "C" int dl3p_pwconv_bwd_data_sb_apply_supported(int M, int K, int N, int bn_act, int with_sums) {
   // (M, K, N) as dl3p_pwconv_bwd_data_sb: K output columns, N the reduction = channels of the folded BatchNorm.  Two kernels serve
   // it: the pinned-schedule form (256 x 256, no accumulation: the call falls back where the caller accumulates) and the
   // row-stationary one
-  if (sb3d_takes(M, K, N, (N + 31) / 32 * 32, bn_act, DL3P_ACT_RELU, with_sums != 0, false) && M >= 131072) return 1;
+  if (sb3d_takes(M, K, N, (N + 31) / 32 * 32, bn_act, DL3P_ACT_RELU, with_sums != 0, false, 0) && M >= 131072) return 1;
   if (M < 131072 || !dl3p_sb_rs_fold_supported(M, N, K, bn_act)) return 0;
   return 1;
 }
@@ -1472,12 +1472,13 @@ extern "C" int dl3p_pwconv_bwd_data_sb_apply(const float* g, int ldg, const floa
     if (rc) return rc;
     DL3P_CHECK_ARG(scale && shift && save_mean && save_invstd && partials && rows_out, "%s: bad BatchNorm arguments", fn);
   }
-  const bool take3 = sb3d_takes(M, K, N, pitch, bn_act, act, bnb, accumulate != 0);
-  DL3P_CHECK_ARG(take3 || dl3p_pwconv_bwd_data_sb_apply_supported(M, K, N, bn_act, bnb), "%s: shape M=%d K=%d N=%d act %d is not served", fn, M, K, N, bn_act);
   int ldm = ldg > ldgx ? ldg : ldgx;
   if (ldz > ldm) ldm = ldz;
   if (ldz_out > ldm) ldm = ldz_out;
   if (lddz > ldm) ldm = lddz;
+  // (the pinned form refuses leading dimensions whose padding rows would wrap; the row-stationary kernel then takes the launch)
+  const bool take3 = sb3d_takes(M, K, N, pitch, bn_act, act, bnb, accumulate != 0, ldm);
+  DL3P_CHECK_ARG(take3 || (M >= 131072 && dl3p_sb_rs_fold_supported(M, N, K, bn_act)), "%s: shape M=%d K=%d N=%d act %d is not served", fn, M, K, N, bn_act);
   DL3P_CHECK_ARG((unsigned long long)M * (unsigned long long)ldm * 4ull < (1ull << 32), "%s: operands of 4 GiB or more are not supported (M=%d)", fn, M);
   GemmParams p = {};
   p.A = g; p.lda = ldg; p.act = DL3P_ACT_NONE;
