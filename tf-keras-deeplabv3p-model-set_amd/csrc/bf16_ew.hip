@@ -272,7 +272,10 @@ inline void pool_plan_b(PoolB& p, int N, int HW, int C) {
   int cs = cv;
   for (int d = 8; d < cv; ++d)
     if (cv % d == 0) { cs = d; break; }
-  if (cs > 256) cs = 256;                      // (C > 1024 with no divisor in [8, 256]: not a shape of these models)
+  // cv > 256 with no divisor in [8, 256] (C = 1028, 2056, ...: not a shape of these models): the slabs still have to tile
+  // every channel, so take the widest divisor below 8 (narrow lanes, but no channel left unreduced)
+  if (cs > 256)
+    for (cs = 7; cv % cs; --cs) {}
   p.cs = cs; p.px = 256 / cs; p.nslab = cv / cs;
   int nchunk = (2 * DL3P_NUM_CUS + N * p.nslab - 1) / (N * p.nslab);
   const int most = (HW + 4 * p.px - 1) / (4 * p.px);
