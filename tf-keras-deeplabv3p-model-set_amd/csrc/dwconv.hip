@@ -29,7 +29,7 @@ struct DwParams {
   long long total;
   int flip, accumulate;
   int nt;              // streaming stores for the output (forward role only)
-  int fast_rows;       // dw_fwd_seg: interior strips on the counted-wait rows (DL3P_DW_FAST_ROWS, default 1)
+  int fast_rows;       // forward launches: take the dw_fwd_seg kernel with counted-wait rows (DL3P_DW_FAST_ROWS, default 1)
   int tw;              // strip width the plan was made for (3x3 window kernels)
   int lat;             // residue-lattice kernels (kind 3): pixels per class and dimension, 2 or 3
   int bf16_io;         // x / w / y / dy are bf16 (the mixed-precision entry at the end of this file; window kernels only)
@@ -106,8 +106,15 @@ __device__ __forceinline__ float4 prologue4(float4 v, float4 sc, float4 sh, int 
 // zero padding are exec-masked loads that never leave the CU (at rate 18 on a 33x33 map a 2x2 output
 // block issues 4 loads instead of 36).  This replaces TF's SpaceToBatchND->conv->BatchToSpaceND
 // (two extra tensor passes) by index arithmetic.
-template <int KS, int TW, int S, int PRO, bool BNB = false, bool UP = false>
-__global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
+// FAST_K (a kernel of its own, chosen by the host from DwParams::fast_rows): interior strips take the counted-wait rows described in
+// front of the row loop below.  Every other launch runs the FAST_K = false kernel, which holds the general row loop and nothing else -- with
+// both bodies in one kernel every instantiation paid 4 to 33 VGPRs for code that two launches of a step use (<3,2,1,2> dropped
+// from three waves per SIMD to two); tests/test_dw_register_budgets.py holds the budgets.
+// (The occupancy bound: the general 5x5 stride-2 kernel behind an activation lands at 256 VGPRs + 38 AGPRs, one wave per SIMD, left to
+// itself; asked for two waves it takes 240 and no scratch.  Every other instantiation compiles as without a bound.)
+template <int KS, int TW, int S, int PRO, bool BNB = false, bool UP = false, bool FAST_K = false>
+__global__ __launch_bounds__(256, (KS == 5 && S == 2 && PRO == 2 && !FAST_K) ? 2 : 1) void dw_fwd_seg(DwParams p) {
+  static_assert(!FAST_K || (PRO != 0 && !BNB && !UP), "counted-wait rows: forward launches only");
   constexpr int SEG = (TW - 1) * S + KS;
   const int b = blockIdx.x;
   const int slab = b / p.nbx;
@@ -204,22 +211,89 @@ __global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
           }
         }
       }
-      // rows of the band that exist on this sub-lattice
-      const int vmax = (p.Ho - py + rate - 1) / rate;
-      const int vend = v1 < vmax ? v1 : vmax;
-      // FAST rows (interior strips of a plain launch: every output column of the strip exists, nothing is accumulated): the loads
-      // of the entering rows are UNCONDITIONAL (row / column clamped into the image; what is outside is zeroed after the prologue,
-      // as always) and so are the stores, and the band's last row (which loads nothing) is a separate copy of the body -- the
-      // compiler can then count: the wait for the entering rows becomes vmcnt(TW), the row's stores stay in flight.  With any
-      // of them under an `if` it waits vmcnt(0) at the top of every row: vmcnt retires in order, so each row also waited for the
-      // round trip of the stores of the row before (csrc/resize_head.hip, resize_fwd_seg_kernel, has the measurement).
-      int coffc[SEG];
+      // FAST rows (FAST_K kernels, interior strips: every output column of the strip exists; the host sends only plain streaming
+      // launches here, nothing is accumulated): the loads of the entering rows are UNCONDITIONAL (row / column clamped into the image;
+      // what is outside is zeroed after the prologue, as always) and so are the stores, and the band's last row (which loads nothing)
+      // is a separate copy of the body -- the compiler can then count: the wait for the entering rows becomes vmcnt(TW), the row's
+      // stores stay in flight.  With any of them under an `if` it waits vmcnt(0) at the top of every row: vmcnt retires in order, so
+      // each row also waited for the round trip of the stores of the row before (csrc/resize_head.hip, resize_fwd_seg_kernel, has the
+      // measurement).  Edge strips of a FAST_K kernel fall through to the general rows below.
+      if constexpr (FAST_K) {
+        if (ox0 + (TW - 1) * rate < p.Wo) {
+          int coffc[SEG];
 #pragma unroll
-      for (int i = 0; i < SEG; ++i) coffc[i] = min(max(ix0 + i * rate, 0), p.W - 1) * p.ldx;
-      auto row = [&](int v, auto fast_c, auto load_c) __attribute__((always_inline)) {
-        constexpr bool FAST = decltype(fast_c)::value, LOAD = decltype(load_c)::value;
+          for (int i = 0; i < SEG; ++i) coffc[i] = min(max(ix0 + i * rate, 0), p.W - 1) * p.ldx;
+          auto row = [&](int v, auto load_c) __attribute__((always_inline)) {
+            constexpr bool LOAD = decltype(load_c)::value;
+            const int oy = py + v * rate;
+            // issue the loads of the S rows that enter the window for the next output row
+            bool nyok[S];
+#pragma unroll
+            for (int q = 0; q < S; ++q) {
+              const int iy = (oy + rate) * S - p.pad_t + (KS - S + q) * rate;
+              nyok[q] = LOAD && iy >= 0 && iy < p.H;
+              if (LOAD) {
+                const float* xrow = ximg + (size_t)min(max(iy, 0), p.H - 1) * p.W * p.ldx;
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) raw[q][i] = ld4(xrow + coffc[i]);
+              }
+            }
+            // the loads stay in front of the row's FMAs (without the branches of the general path around them the scheduler sinks
+            // them next to their use, behind the FMAs)
+            __builtin_amdgcn_sched_barrier(0);
+            float4 acc[TW];
+#pragma unroll
+            for (int i = 0; i < TW; ++i) acc[i] = zero4();
+            // keep the LDS weight reads inside the row loop: hoisted, the 25 vectors cost 100 VGPRs (1 wave per SIMD)
+            if (WLDS) asm volatile("" ::: "memory");
+#pragma unroll
+            for (int ky = 0; ky < KS; ++ky)
+#pragma unroll
+              for (int kx = 0; kx < KS; ++kx) {
+                const float4 wv = wtap(ky * KS + kx);
+#pragma unroll
+                for (int tw = 0; tw < TW; ++tw) acc[tw] = fma4(win[ky][tw * S + kx], wv, acc[tw]);
+              }
+            float* yrow = p.y + (((size_t)n * p.Ho + oy) * p.Wo + ox0) * p.ldy + c;
+#pragma unroll
+            for (int tw = 0; tw < TW; ++tw) {
+              const float4 vv = acc[tw];
+              // (the kind of store is known at compile time -- these launches stream -- so that the stores of a row can be counted)
+              st4_nt(yrow + (size_t)tw * rate * p.ldy, vv);
+              s1[0] = add4(s1[0], vv);
+              s1[1] = fma4(vv, vv, s1[1]);
+            }
+            if (!LOAD) return;
+            __builtin_amdgcn_sched_barrier(0);       // ... and their consumption behind the row's stores
+            // slide the window down by S rows
+#pragma unroll
+            for (int ky = 0; ky + S < KS; ++ky)
+#pragma unroll
+              for (int i = 0; i < SEG; ++i) win[ky][i] = win[ky + S][i];
+#pragma unroll
+            for (int q = 0; q < S; ++q)
+#pragma unroll
+              for (int i = 0; i < SEG; ++i) {
+                float4 a = prologue4<PRO>(raw[q][i], sc, sh, act);
+                // the prologue runs whether or not the pixel is inside the image (left to itself the compiler branches around it,
+                // the wait for raw[q][i] lands inside the branch, and the top of the next row waits vmcnt(0) again)
+                asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+                win[KS - S + q][i] = (nyok[q] && cok[i]) ? a : zero4();
+              }
+          };
+          // rows of the band that exist on this sub-lattice
+          const int vmax = (p.Ho - py + rate - 1) / rate;
+          const int vend = v1 < vmax ? v1 : vmax;
+          for (int v = v0; v + 1 < vend; ++v) row(v, std::true_type{});
+          if (vend > v0) row(vend - 1, std::false_type{});
+          continue;
+        }
+      }
+      // the general rows: all that a FAST_K = false kernel holds
+      for (int v = v0; v < v1; ++v) {
         const int oy = py + v * rate;
-        const bool more = LOAD;
+        if (oy >= p.Ho) break;
+        const bool more = v + 1 < v1 && oy + rate < p.Ho;
         float4 zv[TW];
         if (BNB) {      // z at this row's output pixels: in flight during the FMAs below
           const float* zrow = p.bb_z + (((size_t)n * p.Ho + oy) * p.Wo + ox0) * p.bb_ldz + c;
@@ -232,24 +306,13 @@ __global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
         for (int q = 0; q < S; ++q) {
           const int iy = (oy + rate) * S - p.pad_t + (KS - S + q) * rate;
           nyok[q] = more && iy >= 0 && iy < p.H;
-          if (FAST) {
-            if (LOAD) {
-              const float* xrow = ximg + (size_t)min(max(iy, 0), p.H - 1) * p.W * p.ldx;
+          const float* xrow = ximg + (size_t)iy * p.W * p.ldx;
 #pragma unroll
-              for (int i = 0; i < SEG; ++i) raw[q][i] = ld4(xrow + coffc[i]);
-            }
-          } else {
-            const float* xrow = ximg + (size_t)iy * p.W * p.ldx;
-#pragma unroll
-            for (int i = 0; i < SEG; ++i) {
-              raw[q][i] = zero4();
-              if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
-            }
+          for (int i = 0; i < SEG; ++i) {
+            raw[q][i] = zero4();
+            if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
           }
         }
-        // FAST: the loads stay in front of the row's FMAs (without the branches of the general path around them the scheduler sinks
-        // them next to their use, behind the FMAs)
-        if (FAST) __builtin_amdgcn_sched_barrier(0);
         float4 acc[TW];
 #pragma unroll
         for (int i = 0; i < TW; ++i) acc[i] = zero4();
@@ -266,14 +329,11 @@ __global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
         float* yrow = p.y + (((size_t)n * p.Ho + oy) * p.Wo + ox0) * p.ldy + c;
 #pragma unroll
         for (int tw = 0; tw < TW; ++tw) {
-          if (FAST || ox0 + tw * rate < p.Wo) {
+          if (ox0 + tw * rate < p.Wo) {
             float4 vv = acc[tw];
             float* yp = yrow + (size_t)tw * rate * p.ldy;
-            if (!FAST && p.accumulate) vv = add4(vv, ld4(yp));
-            // (FAST: the kind of store is known at compile time -- forward launches stream, data gradients do not -- so that the
-            // stores of a row can be counted)
-            if (FAST) { if (PRO != 0) st4_nt(yp, vv); else st4(yp, vv); }
-            else if (p.nt) st4_nt(yp, vv); else st4(yp, vv);
+            if (p.accumulate) vv = add4(vv, ld4(yp));
+            if (p.nt) st4_nt(yp, vv); else st4(yp, vv);
             if (BNB) {
               bnb_accumulate(s1, vv, zv[tw], bsc, bsh, bmu, bis, p.bb_act);
             } else {
@@ -282,8 +342,6 @@ __global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
             }
           }
         }
-        if (!LOAD) return;
-        if (FAST) __builtin_amdgcn_sched_barrier(0);       // ... and their consumption behind the row's stores
         // slide the window down by S rows
 #pragma unroll
         for (int ky = 0; ky + S < KS; ++ky)
@@ -293,22 +351,9 @@ __global__ __launch_bounds__(256) void dw_fwd_seg(DwParams p) {
         for (int q = 0; q < S; ++q)
 #pragma unroll
           for (int i = 0; i < SEG; ++i) {
-            float4 a = prologue4<PRO>(raw[q][i], sc, sh, act);
-            // FAST: the prologue runs whether or not the pixel is inside the image (left to itself the compiler branches around
-            // it, the wait for raw[q][i] lands inside the branch, and the top of the next row waits vmcnt(0) again)
-            if (FAST) asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+            const float4 a = prologue4<PRO>(raw[q][i], sc, sh, act);
             win[KS - S + q][i] = (nyok[q] && cok[i]) ? a : zero4();
           }
-      };
-      // (compiled into the forward instantiations only: the rule never sends a data gradient here)
-      constexpr bool HAS_FAST = PRO != 0 && !BNB && !UP;
-      const bool fast = HAS_FAST && !p.accumulate && p.fast_rows && p.nt && ox0 + (TW - 1) * rate < p.Wo;
-      if (HAS_FAST && fast) {
-        for (int v = v0; v + 1 < vend; ++v) row(v, std::true_type{}, std::true_type{});
-        if (vend > v0) row(vend - 1, std::true_type{}, std::false_type{});
-      } else {
-        for (int v = v0; v + 1 < vend; ++v) row(v, std::false_type{}, std::true_type{});
-        if (vend > v0) row(vend - 1, std::false_type{}, std::false_type{});
       }
     }
   }
@@ -603,8 +648,12 @@ __global__ __launch_bounds__(256, 2) void dw5_wgrad_rows(DwParams p) {
 // Same window walk as the forward kernel (the activated input rows live in registers); every output
 // row adds win[ky][tw+kx] * dy[tw] into the k*k per-thread tap accumulators.  One partial row
 // [k*k][C] per workgroup, summed in a fixed order afterwards.
+// Two waves per SIMD asked of the folded (BNA) instantiations: the TW = 4 ones sat at 256 VGPRs + 2 AGPRs without the
+// bound -- 258 rounds up to 264, ONE wave per SIMD, on a kernel that streams ~1 GB per launch; with it they fit 256 with no scratch.
+// The UP kernels (opt-in, measured slower) would spill under that bound; they and the unfolded kernels (two or three waves already)
+// keep the default and compile as before.
 template <int KS, int TW, int S, int PRO, bool BNA = false, bool UP = false>
-__global__ __launch_bounds__(256) void dw_bwd_weight_seg(DwParams p) {
+__global__ __launch_bounds__(256, (BNA && !UP) ? 2 : 1) void dw_bwd_weight_seg(DwParams p) {
   constexpr int SEG = (TW - 1) * S + KS;
   const int b = blockIdx.x;
   const int slab = b / p.nbx;
@@ -1377,8 +1426,15 @@ static void launch_fwd_pro(const DwParams& p, int kind, dim3 grid, hipStream_t s
     const int rows_tw = dw5_rows_tw(ceil_div(p.Wo, p.rate));
     if (kind == 1 && rows_tw == 4) dl3p_launch(dw5_rows<4, PRO>, grid, block, lds, st, p);
     else if (kind == 1 && rows_tw == 2) dl3p_launch(dw5_rows<2, PRO>, grid, block, lds, st, p);
-    else if (kind == 1) dl3p_launch(dw_fwd_seg<5, 2, 1, PRO>, grid, block, lds, st, p);
-    else if (kind == 2) dl3p_launch(dw_fwd_seg<5, 1, 2, PRO>, grid, block, lds, st, p);
+    else if (kind == 1 || kind == 2) {
+      const bool fast = PRO != 0 && p.fast_rows && p.nt && !p.accumulate;
+      if constexpr (PRO != 0) {
+        if (fast && kind == 1) dl3p_launch(dw_fwd_seg<5, 2, 1, PRO, false, false, true>, grid, block, lds, st, p);
+        else if (fast) dl3p_launch(dw_fwd_seg<5, 1, 2, PRO, false, false, true>, grid, block, lds, st, p);
+      }
+      if (!fast && kind == 1) dl3p_launch(dw_fwd_seg<5, 2, 1, PRO>, grid, block, lds, st, p);
+      else if (!fast) dl3p_launch(dw_fwd_seg<5, 1, 2, PRO>, grid, block, lds, st, p);
+    }
     else dl3p_launch(dw_fwd_gather<5, PRO>, grid, block, 0, st, p);
     return;
   }
@@ -1388,6 +1444,15 @@ static void launch_fwd_pro(const DwParams& p, int kind, dim3 grid, hipStream_t s
       else dl3p_launch(dw_fwd_seg<3, 4, 1, 2, false, true>, grid, block, 0, st, p);
     }
     return;
+  }
+  // counted-wait rows: the FAST_K kernels, for plain streaming forward launches only (launch_fwd sets fast_rows)
+  if constexpr (PRO != 0) {
+    if (p.fast_rows && p.nt && !p.accumulate && (kind == 1 || kind == 2)) {
+      if (kind == 1 && p.tw == 2) dl3p_launch(dw_fwd_seg<3, 2, 1, PRO, false, false, true>, grid, block, 0, st, p);
+      else if (kind == 1) dl3p_launch(dw_fwd_seg<3, 4, 1, PRO, false, false, true>, grid, block, 0, st, p);
+      else dl3p_launch(dw_fwd_seg<3, 2, 2, PRO, false, false, true>, grid, block, 0, st, p);
+      return;
+    }
   }
   if (kind == 1 && p.tw == 2) dl3p_launch(dw_fwd_seg<3, 2, 1, PRO>, grid, block, 0, st, p);
   else if (kind == 1) dl3p_launch(dw_fwd_seg<3, 4, 1, PRO>, grid, block, 0, st, p);
