@@ -636,6 +636,33 @@ int dl3p_adam_step(float* w, float* m, float* v, const float* g, size_t n, const
 int dl3p_rmsprop_step(float* w, float* v, const float* g, size_t n, const float* lr_dev, float rho, float epsilon,
                       float grad_scale, const float* l2_elem, const float* lr_scale_elem, void* stream);
 
+/* Averaged optimisers (train.py --average_type, common/model_utils.py:133-172: tensorflow-addons MovingAverage, SWA,
+ * Lookahead) on one more flat slot buffer `avg` of n floats: the average (ema, swa) or Lookahead's slow weights.  The
+ * *_avg entry points are the three steps above with the averaging rule applied to the new weight w' in the same pass;
+ * dl3p_weight_average applies the same rule as a pass of its own behind any update of w.  t = *step_counter is the
+ * 1-based count of the step the call belongs to (read on the device, so a captured launch follows it):
+ *   avg_mode 1 ema:        avg <- avg - (avg - w') * (1 - avg_coef)                       avg_coef = decay; every step
+ *   avg_mode 2 swa:        it = t - 1, ns = max(0, (it - avg_start) / avg_period); when it >= avg_start and
+ *                          it == avg_start + ns * avg_period: avg <- (avg * ns + w') / (ns + 1)   (ns == 0: avg <- w')
+ *   avg_mode 3 lookahead:  when t % avg_period == 0: sb = avg + avg_coef * (w' - avg); avg <- sb; w <- sb
+ * On a step where swa / lookahead do nothing `avg` is neither read nor written.  Elements with lr_scale_elem == 0 keep
+ * their `avg` (and, as above, their weight).  The caller initialises `avg` (Keras creates a slot from the variable).
+ * Every buffer must be 16-byte aligned. */
+int dl3p_sgd_momentum_avg(float* w, float* v, const float* g, size_t n, const float* lr_dev, float momentum,
+                          float l2, float grad_scale, const float* l2_elem, const float* lr_scale_elem,
+                          float* avg, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                          const int64_t* step_counter, void* stream);
+int dl3p_adam_step_avg(float* w, float* m, float* v, const float* g, size_t n, const float* lr_dev,
+                       const int64_t* step_counter, float beta_1, float beta_2, float epsilon, float grad_scale,
+                       const float* l2_elem, const float* lr_scale_elem, float* avg, int avg_mode, float avg_coef,
+                       int avg_period, int avg_start, void* stream);
+int dl3p_rmsprop_step_avg(float* w, float* v, const float* g, size_t n, const float* lr_dev, float rho, float epsilon,
+                          float grad_scale, const float* l2_elem, const float* lr_scale_elem,
+                          float* avg, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                          const int64_t* step_counter, void* stream);
+int dl3p_weight_average(float* w, float* avg, size_t n, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                        const int64_t* step_counter, const float* lr_scale_elem, void* stream);
+
 /* ---------------------------------------------------------------- mixed precision (bf16 storage, fp32 accumulate)
  * train.py:37-46 `--mixed_precision` (the reference sets the Keras global policy; BASELINE.json configs[4] asks for bf16
  * on MobileNetV3-Large 1024x2048).  The *_bf16 entry points are the twins of the calls above for tensors stored as

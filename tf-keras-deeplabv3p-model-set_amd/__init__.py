@@ -7,11 +7,13 @@ importlib:  importlib.import_module('tf-keras-deeplabv3p-model-set_amd')  -- or 
 """
 from .model import (get_deeplabv3p_model, deeplab_model_map, DeeplabModel, SGD, Adam, RMSprop, get_optimizer,  # noqa: F401
                     SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy, SparseSoftmaxFocalLoss,
-                    miou_from_confusion, Jaccard, jaccard_from_counts, EvalCallBack)
+                    miou_from_confusion, Jaccard, jaccard_from_counts, EvalCallBack, MovingAverage, SWA, Lookahead,
+                    AverageModelCheckpoint)
 
 from . import mixed_precision  # noqa: F401,E402
 from . import watchdog  # noqa: F401,E402
 
 __all__ = ['get_deeplabv3p_model', 'deeplab_model_map', 'DeeplabModel', 'SGD', 'Adam', 'RMSprop', 'get_optimizer',
            'SparseCategoricalCrossEntropy', 'WeightedSparseCategoricalCrossEntropy', 'SparseSoftmaxFocalLoss',
-           'miou_from_confusion', 'Jaccard', 'jaccard_from_counts', 'EvalCallBack', 'mixed_precision']
+           'miou_from_confusion', 'Jaccard', 'jaccard_from_counts', 'EvalCallBack', 'MovingAverage', 'SWA', 'Lookahead',
+           'AverageModelCheckpoint', 'mixed_precision']

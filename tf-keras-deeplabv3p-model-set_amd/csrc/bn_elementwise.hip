@@ -1267,3 +1267,250 @@ extern "C" int dl3p_rmsprop_step(float* w, float* v, const float* g, size_t n, c
   return DL3P_OK;
 }
 
+// ------------------------------------------------------------------------------ averaged optimisers
+// train.py --average_type {ema,swa,lookahead} (common/model_utils.py:133-172: tensorflow-addons MovingAverage(0.99),
+// SWA(start 0, period 10), Lookahead(sync 6, step 0.5)) on one more flat slot buffer `avg` (the average, or Lookahead's slow
+// weights).  t = *step_counter is the 1-based step the optimiser kernel runs in (tfa's `iterations` inside the op is t - 1),
+// w' the weight after the wrapped optimiser's own update of this step; float32 in the written order:
+//   1 ema:        avg <- avg - (avg - w') * (1 - decay)                                      every step
+//   2 swa:        it = t - 1, ns = max(0, (it - start) / period); when it >= start and it == start + ns * period:
+//                 avg <- (avg * ns + w') / (ns + 1)      (ns == 0: avg <- w', exactly)      else avg is left alone
+//   3 lookahead:  when t % sync_period == 0: sb = slow + alpha * (w' - slow), slow <- sb, w <- sb   else both left alone
+// What a step does is decided once per launch from the device counter (the same for every lane), so a captured launch is
+// right in every replay; on a step that does nothing `avg` is neither read nor written.  Elements with lr_scale_elem == 0
+// have no slot in tfa: their `avg` keeps the value it was initialised with.
+__device__ __forceinline__ float avg_rule_ema(float avg, float w, float decay) { return avg - (avg - w) * (1.f - decay); }
+__device__ __forceinline__ float avg_rule_swa(float avg, float w, float ns) { return ns == 0.f ? w : (avg * ns + w) / (ns + 1.f); }
+__device__ __forceinline__ float avg_rule_lookahead(float slow, float w, float alpha) { return slow + alpha * (w - slow); }
+
+struct AvgArgs { float* avg; int mode; float coef; int period, start; const int64_t* step; };
+
+// -> the rule this launch applies (0: none) and swa's snapshot count
+__device__ __forceinline__ int avg_decide(const AvgArgs& a, float* ns) {
+  const int64_t t = *a.step;
+  *ns = 0.f;
+  if (a.mode == 1) return 1;
+  if (a.mode == 2) {
+    const int64_t it = t - 1;
+    if (it < a.start) return 0;
+    const int64_t k = (it - a.start) / a.period;
+    if (it != a.start + k * a.period) return 0;
+    *ns = (float)k;
+    return 2;
+  }
+  return (a.mode == 3 && t % a.period == 0) ? 3 : 0;
+}
+
+// one element: the new slot value; Lookahead also replaces the weight
+__device__ __forceinline__ void avg_apply(int act, float& w, float& avg, float coef, float ns) {
+  if (act == 1) avg = avg_rule_ema(avg, w, coef);
+  else if (act == 2) avg = avg_rule_swa(avg, w, ns);
+  else { avg = avg_rule_lookahead(avg, w, coef); w = avg; }
+}
+
+struct OptAvgArgs {
+  float* w; float* s1; float* s2; const float* g;       // s1: SGD velocity / Adam m; s2: Adam / RMSprop v
+  size_t n4, n;
+  const float* lr_dev; const int64_t* step;
+  float c0, c1, c2, l2, gscale;                         // SGD: momentum; Adam: beta_1, beta_2, eps; RMSprop: -, rho, eps
+  const float* l2e; const float* lre;
+  AvgArgs a;
+};
+
+// the update of sgd_kernel (KIND 0) / adaptive_kernel<true> (1) / adaptive_kernel<false> (2) on one element, operation for operation
+template <int KIND>
+__device__ __forceinline__ void opt_elem(float& w, float& s1, float& s2, float g, float d, float alpha, const OptAvgArgs& p) {
+  if (KIND == 0) {
+    const float nv = p.c0 * s1 - alpha * fmaf(g, p.gscale, 2.f * d * w);
+    s1 = nv;
+    w = w + nv;
+  } else {
+    const float gg = fmaf(g, p.gscale, 2.f * d * w);
+    if (KIND == 1) {
+      const float m = p.c0 * s1 + (1.f - p.c0) * gg;
+      const float v = p.c1 * s2 + (1.f - p.c1) * gg * gg;
+      s1 = m;
+      s2 = v;
+      w = w - alpha * m / (sqrtf(v) + p.c2);
+    } else {
+      const float v = p.c1 * s2 + (1.f - p.c1) * gg * gg;
+      s2 = v;
+      w = w - alpha * gg * rsqrtf(v + p.c2);
+    }
+  }
+}
+
+// optimiser step and averaging rule in one pass: w' stays in registers between the two
+template <int KIND>
+__global__ __launch_bounds__(256) void opt_avg_kernel(OptAvgArgs p) {
+  __shared__ float alpha_s;
+  if (threadIdx.x == 0) {
+    float a = *p.lr_dev;
+    if (KIND == 1) {
+      const double t = (double)*p.step;
+      a = (float)((double)a * sqrt(1.0 - pow((double)p.c1, t)) / (1.0 - pow((double)p.c0, t)));
+    }
+    alpha_s = a;
+  }
+  __syncthreads();
+  const float alpha = alpha_s;
+  float ns;
+  const int act = avg_decide(p.a, &ns);
+  const float coef = p.a.coef;
+  const float dflt_l2 = KIND == 0 ? p.l2 : 0.f;
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (; i < p.n4; i += stride) {
+    const float4 w4 = ld4(p.w + i * 4), g4 = ld4(p.g + i * 4);
+    const float4 a4 = KIND != 2 ? ld4(p.s1 + i * 4) : zero4();
+    const float4 b4 = KIND != 0 ? ld4(p.s2 + i * 4) : zero4();
+    const float4 d4 = p.l2e ? ld4(p.l2e + i * 4) : make_float4(dflt_l2, dflt_l2, dflt_l2, dflt_l2);
+    const float4 m4 = p.lre ? ld4(p.lre + i * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
+    const float4 v4 = act ? ld4(p.a.avg + i * 4) : zero4();
+    float w[4] = {w4.x, w4.y, w4.z, w4.w}, s1[4] = {a4.x, a4.y, a4.z, a4.w}, s2[4] = {b4.x, b4.y, b4.z, b4.w};
+    float av[4] = {v4.x, v4.y, v4.z, v4.w};
+    const float g[4] = {g4.x, g4.y, g4.z, g4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w}, m[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float nw = w[k], n1 = s1[k], n2 = s2[k], na = av[k];
+      opt_elem<KIND>(nw, n1, n2, g[k], d[k], alpha, p);
+      if (act) avg_apply(act, nw, na, coef, ns);
+      const bool on = m[k] != 0.f;              // a frozen element keeps weight, moments and slot
+      w[k] = on ? nw : w[k]; s1[k] = on ? n1 : s1[k]; s2[k] = on ? n2 : s2[k]; av[k] = on ? na : av[k];
+    }
+    if (KIND != 2) st4(p.s1 + i * 4, make_float4(s1[0], s1[1], s1[2], s1[3]));
+    if (KIND != 0) st4(p.s2 + i * 4, make_float4(s2[0], s2[1], s2[2], s2[3]));
+    st4(p.w + i * 4, make_float4(w[0], w[1], w[2], w[3]));
+    if (act) st4(p.a.avg + i * 4, make_float4(av[0], av[1], av[2], av[3]));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (p.n - p.n4 * 4)) {   // scalar tail
+    const size_t j = p.n4 * 4 + threadIdx.x;
+    if (!p.lre || p.lre[j] != 0.f) {
+      float nw = p.w[j], n1 = KIND != 2 ? p.s1[j] : 0.f, n2 = KIND != 0 ? p.s2[j] : 0.f;
+      opt_elem<KIND>(nw, n1, n2, p.g[j], p.l2e ? p.l2e[j] : dflt_l2, alpha, p);
+      if (act) {
+        float na = p.a.avg[j];
+        avg_apply(act, nw, na, coef, ns);
+        p.a.avg[j] = na;
+      }
+      if (KIND != 2) p.s1[j] = n1;
+      if (KIND != 0) p.s2[j] = n2;
+      p.w[j] = nw;
+    }
+  }
+}
+
+// the same rules as a pass of their own behind any optimiser
+__global__ __launch_bounds__(256) void weight_average_kernel(float* __restrict__ w, size_t n4, size_t n,
+                                                             const float* __restrict__ lre, AvgArgs a) {
+  float ns;
+  const int act = avg_decide(a, &ns);
+  if (!act) return;
+  const float coef = a.coef;
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (; i < n4; i += stride) {
+    const float4 w4 = ld4(w + i * 4), v4 = ld4(a.avg + i * 4);
+    const float4 m4 = lre ? ld4(lre + i * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
+    float ww[4] = {w4.x, w4.y, w4.z, w4.w}, av[4] = {v4.x, v4.y, v4.z, v4.w};
+    const float m[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float nw = ww[k], na = av[k];
+      avg_apply(act, nw, na, coef, ns);
+      const bool on = m[k] != 0.f;
+      ww[k] = on ? nw : ww[k]; av[k] = on ? na : av[k];
+    }
+    st4(a.avg + i * 4, make_float4(av[0], av[1], av[2], av[3]));
+    if (act == 3) st4(w + i * 4, make_float4(ww[0], ww[1], ww[2], ww[3]));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {   // scalar tail
+    const size_t j = n4 * 4 + threadIdx.x;
+    if (!lre || lre[j] != 0.f) {
+      float nw = w[j], na = a.avg[j];
+      avg_apply(act, nw, na, coef, ns);
+      a.avg[j] = na;
+      if (act == 3) w[j] = nw;
+    }
+  }
+}
+
+static int check_avg(const char* fn, const float* avg, int avg_mode, int avg_period, const int64_t* step_counter) {
+  DL3P_CHECK_ARG(avg && step_counter, "%s: null pointer", fn);
+  DL3P_CHECK_ARG(aligned16(avg), "%s: buffers must be 16-byte aligned", fn);
+  DL3P_CHECK_ARG(avg_mode >= 1 && avg_mode <= 3, "%s: avg_mode %d is not 1 (ema), 2 (swa) or 3 (lookahead)", fn, avg_mode);
+  DL3P_CHECK_ARG(avg_period >= 1, "%s: avg_period %d must be at least 1", fn, avg_period);
+  return DL3P_OK;
+}
+
+static unsigned opt_avg_blocks(size_t n) {
+  size_t blocks = (n / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 4096) blocks = 4096;
+  return (unsigned)blocks;
+}
+
+extern "C" int dl3p_sgd_momentum_avg(float* w, float* v, const float* g, size_t n, const float* lr_dev, float momentum,
+                                     float l2, float grad_scale, const float* l2_elem, const float* lr_scale_elem,
+                                     float* avg, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                                     const int64_t* step_counter, void* stream) {
+  DL3P_CHECK_ARG(w && v && g && lr_dev, "dl3p_sgd_momentum_avg: null pointer");
+  DL3P_CHECK_ARG(aligned16(w) && aligned16(v) && aligned16(g) && aligned16(l2_elem) && aligned16(lr_scale_elem),
+                 "dl3p_sgd_momentum_avg: buffers must be 16-byte aligned");
+  int rc = check_avg("dl3p_sgd_momentum_avg", avg, avg_mode, avg_period, step_counter);
+  if (rc) return rc;
+  if (n == 0) return DL3P_OK;
+  OptAvgArgs p = {w, v, nullptr, g, n / 4, n, lr_dev, step_counter, momentum, 0.f, 0.f, l2, grad_scale, l2_elem, lr_scale_elem,
+                  {avg, avg_mode, avg_coef, avg_period, avg_start, step_counter}};
+  hipLaunchKernelGGL((opt_avg_kernel<0>), dim3(opt_avg_blocks(n)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_sgd_momentum_avg");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_adam_step_avg(float* w, float* m, float* v, const float* g, size_t n, const float* lr_dev,
+                                  const int64_t* step_counter, float beta_1, float beta_2, float epsilon, float grad_scale,
+                                  const float* l2_elem, const float* lr_scale_elem, float* avg, int avg_mode, float avg_coef,
+                                  int avg_period, int avg_start, void* stream) {
+  DL3P_CHECK_ARG(w && m && v && g && lr_dev, "dl3p_adam_step_avg: null pointer");
+  DL3P_CHECK_ARG(aligned16(w) && aligned16(m) && aligned16(v) && aligned16(g) && aligned16(l2_elem) && aligned16(lr_scale_elem),
+                 "dl3p_adam_step_avg: buffers must be 16-byte aligned");
+  int rc = check_avg("dl3p_adam_step_avg", avg, avg_mode, avg_period, step_counter);
+  if (rc) return rc;
+  if (n == 0) return DL3P_OK;
+  OptAvgArgs p = {w, m, v, g, n / 4, n, lr_dev, step_counter, beta_1, beta_2, epsilon, 0.f, grad_scale, l2_elem, lr_scale_elem,
+                  {avg, avg_mode, avg_coef, avg_period, avg_start, step_counter}};
+  hipLaunchKernelGGL((opt_avg_kernel<1>), dim3(opt_avg_blocks(n)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_adam_step_avg");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_rmsprop_step_avg(float* w, float* v, const float* g, size_t n, const float* lr_dev, float rho,
+                                     float epsilon, float grad_scale, const float* l2_elem, const float* lr_scale_elem,
+                                     float* avg, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                                     const int64_t* step_counter, void* stream) {
+  DL3P_CHECK_ARG(w && v && g && lr_dev, "dl3p_rmsprop_step_avg: null pointer");
+  DL3P_CHECK_ARG(aligned16(w) && aligned16(v) && aligned16(g) && aligned16(l2_elem) && aligned16(lr_scale_elem),
+                 "dl3p_rmsprop_step_avg: buffers must be 16-byte aligned");
+  int rc = check_avg("dl3p_rmsprop_step_avg", avg, avg_mode, avg_period, step_counter);
+  if (rc) return rc;
+  if (n == 0) return DL3P_OK;
+  OptAvgArgs p = {w, nullptr, v, g, n / 4, n, lr_dev, step_counter, 0.f, rho, epsilon, 0.f, grad_scale, l2_elem, lr_scale_elem,
+                  {avg, avg_mode, avg_coef, avg_period, avg_start, step_counter}};
+  hipLaunchKernelGGL((opt_avg_kernel<2>), dim3(opt_avg_blocks(n)), dim3(256), 0, (hipStream_t)stream, p);
+  DL3P_CHECK_LAUNCH("dl3p_rmsprop_step_avg");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_weight_average(float* w, float* avg, size_t n, int avg_mode, float avg_coef, int avg_period, int avg_start,
+                                   const int64_t* step_counter, const float* lr_scale_elem, void* stream) {
+  DL3P_CHECK_ARG(w, "dl3p_weight_average: null pointer");
+  DL3P_CHECK_ARG(aligned16(w) && aligned16(lr_scale_elem), "dl3p_weight_average: buffers must be 16-byte aligned");
+  int rc = check_avg("dl3p_weight_average", avg, avg_mode, avg_period, step_counter);
+  if (rc) return rc;
+  if (n == 0) return DL3P_OK;
+  AvgArgs a = {avg, avg_mode, avg_coef, avg_period, avg_start, step_counter};
+  hipLaunchKernelGGL(weight_average_kernel, dim3(opt_avg_blocks(n)), dim3(256), 0, (hipStream_t)stream, w, n / 4, n,
+                     lr_scale_elem, a);
+  DL3P_CHECK_LAUNCH("dl3p_weight_average");
+  return DL3P_OK;
+}

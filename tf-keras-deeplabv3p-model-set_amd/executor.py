@@ -48,6 +48,12 @@ class ParamStore:
         self.G = torch.zeros(off, **f)
         self.V = torch.zeros(off, **f)
         self.V2 = None                        # second-moment buffer, allocated when Adam asks for it
+        # slot of an averaged optimiser (model.MovingAverage / SWA: the average; Lookahead: the slow weights), allocated when
+        # one is compiled.  Keras creates slots from the variables at the first step of a NEW optimizer object: A_pending says
+        # that A still has to be taken from P then (Executor.train_step), so weights loaded after compile() are honoured.
+        # upload() / set_weights / load_weights never touch A.
+        self.A = None
+        self.A_pending = False
         # optimiser iteration counter (Adam's bias correction, the dropout stream): one per model, shared by the
         # executors of every batch size, so a last partial batch continues the count instead of restarting it
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
@@ -383,7 +389,8 @@ class Probe:
 
 class Executor:
     def __init__(self, graph, head, store, batch, training, num_classes, ignore_index=255, dist=None,
-                 seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False):
+                 seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
+                 averaging=None):
         self.g, self.head, self.store = graph, head, store
         self.N, self.training, self.C = batch, training, num_classes
         self.ignore_index = ignore_index
@@ -404,6 +411,15 @@ class Executor:
         self.seed, self.momentum = seed, (self.optimizer[1] if self.optimizer[0] == 'sgd' else 0.0)
         if self.optimizer[0] == 'adam' and store.V2 is None:
             store.V2 = torch.zeros_like(store.V)
+        # averaging: None | ('ema', decay) | ('swa', start, period) | ('lookahead', sync_period, alpha)  (model avg_spec())
+        # -> (avg_mode, avg_coef, avg_period, avg_start) of the dl3p_*_avg entry points
+        self.averaging = None
+        if averaging is not None and training:
+            self.averaging = {'ema': lambda d: (1, float(d), 1, 0), 'swa': lambda s, p: (2, 0.0, int(p), int(s)),
+                              'lookahead': lambda k, a: (3, float(a), int(k), 0)}[averaging[0]](*averaging[1:])
+            if store.A is None:
+                store.A = torch.zeros_like(store.P)
+                store.A_pending = True
         self.dev = store.device
         self.L = lib()
         # which batch variance feeds BatchNormalization's moving average (dl3p_bn_finalize update_moving): 1 biased (Keras
@@ -429,6 +445,7 @@ class Executor:
         # tracing runs every kernel once on zero inputs: keep the weights / optimiser state intact
         snap_p, snap_v, snap_step, snap_ostep = store.P.clone(), store.V.clone(), store.step.clone(), store.opt_step.clone()
         snap_v2 = store.V2.clone() if store.V2 is not None else None
+        snap_a, snap_pending = (store.A.clone() if store.A is not None else None), store.A_pending
         if training:
             self.fwd = self._trace_forward()
             self.bwd = self._trace_backward()
@@ -440,6 +457,9 @@ class Executor:
         store.V.copy_(snap_v)
         if snap_v2 is not None:
             store.V2.copy_(snap_v2)
+        if snap_a is not None:
+            store.A.copy_(snap_a)
+        store.A_pending = snap_pending
         store.transpose()
         store.step.copy_(snap_step)
         store.opt_step.copy_(snap_ostep)
@@ -835,7 +855,7 @@ class Executor:
         train = self.training
         if train:
             P.k(L.increment_counter, self.step.data_ptr())
-            if self.optimizer[0] == 'adam':
+            if self.optimizer[0] == 'adam' or self.averaging is not None:      # (the averaging rules are gated by it too)
                 P.k(L.increment_counter, self.store.opt_step.data_ptr())
         self._fwd_pending, self._fwd_stage_off = [], 0
         self._irb_stage = {}
@@ -1991,7 +2011,23 @@ class Executor:
         if self.dist is not None:
             scale = 1.0 / self.dist.world_size
         kind = self.optimizer[0]
-        if kind == 'adam':
+        if self.averaging is not None:
+            # the averaging rule in the same pass as the update (dl3p_*_avg), ahead of the mirror refreshes below: after a
+            # Lookahead sync every mirror is made from the synced weights
+            mode, coef, period, start = self.averaging
+            avg = (st.A.data_ptr(), mode, coef, period, start)
+            if kind == 'adam':
+                _, b1, b2, eps = self.optimizer
+                P.k(L.adam_step_avg, st.P.data_ptr(), st.V.data_ptr(), st.V2.data_ptr(), st.G.data_ptr(), st.total,
+                    self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg)
+            elif kind == 'rmsprop':
+                _, rho, eps = self.optimizer
+                P.k(L.rmsprop_step_avg, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(), rho, eps,
+                    scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
+            else:
+                P.k(L.sgd_momentum_avg, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(),
+                    float(self.momentum), 0.0, scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
+        elif kind == 'adam':
             _, b1, b2, eps = self.optimizer
             P.k(L.adam_step, st.P.data_ptr(), st.V.data_ptr(), st.V2.data_ptr(), st.G.data_ptr(), st.total,
                 self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, st.l2.data_ptr(), st.lr_scale.data_ptr())
@@ -2115,6 +2151,9 @@ class Executor:
     def train_step(self):
         self._sb_sync()
         self._pin_options()
+        if self.averaging is not None and self.store.A_pending:     # the slot of a new averaged optimiser starts from the weights
+            self.store.A.copy_(self.store.P)
+            self.store.A_pending = False
         self.fwd.run()
         self.bwd.run()
         self.opt.run()

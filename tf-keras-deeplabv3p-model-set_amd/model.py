@@ -102,13 +102,109 @@ class RMSprop(SGD):
         return ('rmsprop', float(self.rho), float(self.epsilon))
 
 
+class _AveragedOptimizer:
+    """tensorflow-addons' optimizer wrappers (common/model_utils.py:133-172): the wrapped optimizer does its own update, the
+    wrapper's rule then runs on the new weights in the same kernel (dl3p_*_avg).  learning_rate, lr_at, iterations and
+    spec() are the wrapped optimizer's; avg_spec() is what the executor needs of the rule."""
+
+    def __init__(self, optimizer, kwargs):
+        if not isinstance(optimizer, SGD) or isinstance(optimizer, _AveragedOptimizer):
+            raise ValueError('an averaged optimizer wraps SGD, Adam or RMSprop')
+        if kwargs:
+            raise ValueError('%s: %s not built (the reference passes none of them)'
+                             % (type(self).__name__, ', '.join(sorted(kwargs))))
+        self._optimizer = optimizer
+
+    @property
+    def learning_rate(self):
+        return self._optimizer.learning_rate
+
+    @learning_rate.setter
+    def learning_rate(self, value):
+        self._optimizer.learning_rate = value
+
+    @property
+    def iterations(self):
+        return self._optimizer.iterations
+
+    @iterations.setter
+    def iterations(self, value):
+        self._optimizer.iterations = value
+
+    def lr_at(self, step):
+        return self._optimizer.lr_at(step)
+
+    def spec(self):
+        return self._optimizer.spec()
+
+
+class MovingAverage(_AveragedOptimizer):
+    """tfa.optimizers.MovingAverage(optimizer, average_decay=0.99): average <- average - (average - w) * (1 - decay) after
+    every step (Keras moving_average_update, no zero-debias)"""
+
+    def __init__(self, optimizer, average_decay=0.99, num_updates=None, start_step=0, dynamic_decay=False, **kwargs):
+        if num_updates is not None or dynamic_decay or start_step:
+            raise ValueError('MovingAverage num_updates / dynamic_decay / start_step are not built (the reference passes '
+                             'average_decay only)')
+        super().__init__(optimizer, kwargs)
+        self.average_decay = average_decay
+
+    def avg_spec(self):
+        return ('ema', float(self.average_decay))
+
+
+class SWA(_AveragedOptimizer):
+    """tfa.optimizers.SWA(optimizer, start_averaging=0, average_period=10): a running mean of the weights at iterations
+    start, start + period, start + 2 period, ... (iteration = step - 1)"""
+
+    def __init__(self, optimizer, start_averaging=0, average_period=10, **kwargs):
+        if average_period < 1:
+            raise ValueError('average_period must be >= 1')
+        if start_averaging < 0:
+            raise ValueError('start_averaging must be >= 0')
+        super().__init__(optimizer, kwargs)
+        self.start_averaging, self.average_period = start_averaging, average_period
+
+    def avg_spec(self):
+        return ('swa', int(self.start_averaging), int(self.average_period))
+
+
+class Lookahead(_AveragedOptimizer):
+    """tfa.optimizers.Lookahead(optimizer, sync_period=6, slow_step_size=0.5): every sync_period steps
+    slow <- slow + slow_step_size * (w - slow) and the weights are set to slow"""
+
+    def __init__(self, optimizer, sync_period=6, slow_step_size=0.5, **kwargs):
+        if sync_period < 1:
+            raise ValueError('sync_period must be >= 1')
+        super().__init__(optimizer, kwargs)
+        self.sync_period, self.slow_step_size = sync_period, slow_step_size
+
+    def avg_spec(self):
+        return ('lookahead', int(self.sync_period), float(self.slow_step_size))
+
+
+def get_averaged_optimizer(average_type, optimizer):
+    """common/model_utils.py:133-172 with the reference's constants"""
+    average_type = average_type.lower()
+    if average_type == 'ema':
+        return MovingAverage(optimizer, average_decay=0.99)
+    if average_type == 'swa':
+        return SWA(optimizer, start_averaging=0, average_period=10)
+    if average_type == 'lookahead':
+        return Lookahead(optimizer, sync_period=6, slow_step_size=0.5)
+    raise ValueError('Unsupported average type')
+
+
 def get_optimizer(optim_type, learning_rate, average_type=None, decay_type=None, decay_steps=100000):
-    """common/model_utils.py:112-130: 'sgd' (momentum 0.9), 'adam', 'rmsprop' with the four learning-rate schedules"""
+    """common/model_utils.py:112-172: 'sgd' (momentum 0.9), 'adam', 'rmsprop' with the four learning-rate schedules, wrapped
+    by average_type 'ema' | 'swa' | 'lookahead'"""
     optim_type = optim_type.lower()
     if optim_type not in ('sgd', 'adam', 'rmsprop'):
         raise ValueError('Unsupported optimizer type')
     if average_type:
-        raise ValueError('averaged optimizers are out of scope')
+        if not isinstance(average_type, str) or average_type.lower() not in ('ema', 'swa', 'lookahead'):
+            raise ValueError('Unsupported average type')
+        return get_averaged_optimizer(average_type, get_optimizer(optim_type, learning_rate, None, decay_type, decay_steps))
     lr = learning_rate
     if decay_type:
         d = decay_type.lower()
@@ -453,7 +549,51 @@ class DeeplabModel:
                 if self._store.V2 is not None:
                     self._store.V2.zero_()
                 self._store.opt_step.zero_()       # (the dropout stream, store.step, keeps counting)
+                # the slot of an averaged optimizer belongs to the object too: a new one takes it from the weights at its
+                # first step (ParamStore.A_pending), a plain one has none
+                if self._avg_spec() is None:
+                    self._store.A, self._store.A_pending = None, False
+                elif self._store.A is not None:
+                    self._store.A_pending = True
         return self
+
+    def _avg_spec(self):
+        spec = getattr(self.optimizer, 'avg_spec', None)
+        return spec() if spec is not None else None
+
+    def _averaging_store(self, what):
+        if self._avg_spec() is None:
+            raise RuntimeError('%s: the compiled optimizer does not average weights' % what)
+        store = self._ensure_store()
+        if store.A is None:                # compiled, no executor yet: the slot is created like the first step would
+            import torch
+            store.A, store.A_pending = torch.zeros_like(store.P), True
+        return store
+
+    def get_average_weights(self):
+        """the slot of the averaged optimizer in get_weights() order: the averages of MovingAverage / SWA, the slow weights of
+        Lookahead.  Entries the optimizer does not update (frozen layers, BatchNorm moving statistics) have no slot in
+        tensorflow-addons; here they hold the value the slot buffer was created with.  Before the first step of a new
+        optimizer object that is the current weights."""
+        store = self._averaging_store('get_average_weights')
+        buf = store.P if store.A_pending else store.A
+        return [store.get(p, buf) for p in self._keras_params()]
+
+    def assign_average_vars(self):
+        """tfa `optimizer.assign_average_vars(model.variables)` (MovingAverage, SWA): the weights become the averages, on
+        the device, and every weight mirror is rebuilt.  Variables without a slot (frozen layers, BatchNorm moving
+        statistics) keep their current value, and the slot buffer's copy of them is brought up to date with it, so that
+        get_average_weights() describes the model that was just assigned."""
+        store = self._averaging_store('assign_average_vars')
+        if self._avg_spec()[0] == 'lookahead':
+            raise RuntimeError('assign_average_vars: Lookahead keeps slow weights, not averages (tfa has no such method)')
+        if store.A_pending:
+            return                          # no step yet: the averages are the weights
+        import torch
+        merged = torch.where(store.lr_scale != 0, store.A, store.P)
+        store.P.copy_(merged)
+        store.A.copy_(merged)
+        store.transpose()
 
     def _ensure_store(self):
         import torch
@@ -468,7 +608,8 @@ class DeeplabModel:
         return self._store
 
     def _executor(self, batch, training):
-        key = (batch, training)
+        avg = self._avg_spec() if training else None
+        key = (batch, training) if avg is None else (batch, training, avg)
         if key not in self._exec:
             from .executor import Executor
             store = self._ensure_store()
@@ -479,7 +620,7 @@ class DeeplabModel:
                                        ignore_index=ignore, dist=self.dist if training else None,
                                        seed=self.seed + 7919 * rank, loss=loss_spec(self.loss), optimizer=opt,
                                        sample_weighted=getattr(self, 'sample_weight_mode', None) == 'temporal',
-                                       class_counts=getattr(self, '_jaccard', False))
+                                       class_counts=getattr(self, '_jaccard', False), averaging=avg)
         return self._exec[key]
 
     def train_on_batch(self, x, y, sample_weight=None, return_tensor=False):
@@ -946,3 +1087,63 @@ class EvalCallBack:
             self.model.save(os.path.join(self.log_dir, name.format(
                 epoch=epoch + 1, loss=logs.get('loss', nan), Jaccard=logs.get('Jaccard', nan),
                 val_loss=logs.get('val_loss', nan), val_Jaccard=logs.get('val_Jaccard', nan), mIOU=mIOU)))
+
+
+class AverageModelCheckpoint:
+    """tfa.callbacks.AverageModelCheckpoint (train.py:198-211) for `fit`, in tfa's order: every `period` epochs the averages
+    are assigned to the weights FIRST (update_weights=False keeps a device copy of the weights to put back afterwards),
+    then Keras' ModelCheckpoint logic runs on them -- the best-only test on `monitor`, `model.save` / `save_weights` under
+    `filepath` formatted with epoch + 1 and the logs.  With update_weights=True the weights are therefore replaced by
+    the averages at every such epoch end, whether or not a file is written.  Optimizer slots are not part of the file."""
+
+    def __init__(self, filepath, update_weights, monitor='val_loss', mode='min', verbose=0, save_weights_only=False,
+                 save_best_only=False, period=1):
+        if mode not in ('auto', 'min', 'max'):
+            raise ValueError("mode must be 'auto', 'min' or 'max'")
+        self.filepath, self.update_weights, self.monitor, self.verbose = filepath, update_weights, monitor, verbose
+        self.save_weights_only, self.save_best_only, self.period = save_weights_only, save_best_only, period
+        if mode == 'auto':
+            mode = 'max' if ('acc' in monitor or monitor.startswith('fmeasure')) else 'min'
+        self.better = (lambda a, b: a > b) if mode == 'max' else (lambda a, b: a < b)
+        self.best = -np.inf if mode == 'max' else np.inf
+        self.epochs_since_last_save = 0
+        self.saved = []
+        self.model = None
+
+    def set_model(self, model):
+        self.model = model
+
+    def on_epoch_end(self, epoch, logs=None):
+        self.epochs_since_last_save += 1
+        if self.epochs_since_last_save < self.period:
+            return
+        self.epochs_since_last_save = 0
+        store = self.model._averaging_store('AverageModelCheckpoint')
+        keep = None if self.update_weights else store.P.clone()
+        self.model.assign_average_vars()
+        try:
+            self._save_model(epoch, logs or {})
+        finally:
+            if keep is not None:
+                store.P.copy_(keep)
+                store.transpose()
+
+    def _save_model(self, epoch, logs):
+        path = self.filepath.format(epoch=epoch + 1, **logs)
+        if self.save_best_only:
+            current = logs.get(self.monitor)
+            if current is None:
+                print('Can save best model only with %s available, skipping.' % self.monitor)
+                return
+            if not self.better(current, self.best):
+                if self.verbose:
+                    print('Epoch %05d: %s did not improve from %0.5f' % (epoch + 1, self.monitor, self.best))
+                return
+            if self.verbose:
+                print('Epoch %05d: %s improved from %0.5f to %0.5f, saving model to %s'
+                      % (epoch + 1, self.monitor, self.best, current, path))
+            self.best = current
+        elif self.verbose:
+            print('Epoch %05d: saving model to %s' % (epoch + 1, path))
+        (self.model.save_weights if self.save_weights_only else self.model.save)(path)
+        self.saved.append(path)
