@@ -807,6 +807,19 @@ int dl3p_irb_set_bwd_plan(int want_waves_sums, int want_workgroups_data);
 int dl3p_irb_get_plan(int which);
 int dl3p_irb_selftest(float* out128, void* stream);
 
+/* ---------------------------------------------------------------- fused ghost-module forward (csrc/ghost_fwd.hip)
+ * GhostModule of deeplabv3p_ghostnet.py:135-153 (ratio 2, dw_size 3) with BatchNorm coefficients that are known before the launch
+ * (inference, or frozen layers), as ONE launch in place of dl3p_pwconv_fwd + dl3p_dwconv2d_fwd:
+ *   z1 = a W1, a = in_act(x * in_scale + in_shift) (NULL scale / shift: identity)           -> y[..., 0:C)
+ *   z2 = DepthwiseConv2D(3x3, stride 1, 'same')(act1(z1 * s1 + h1)), taps outside the image 0 -> y[..., C:2C)
+ * x [N][H][W][ldx] (K channels read), y [N][H][W][ldy] (2C channels written, nothing else touched), w1 [K][C], wdw [9][C];
+ * ldx, ldy and C multiples of 4, x and y 16-byte aligned.  K in {16, 24} with C <= 48, K in {48, 72} with C <= 16.
+ * dl3p_ghost_fwd_supported: 1 where dl3p_ghost_fwd has a kernel; anything else returns DL3P_EINVAL without launching. */
+int dl3p_ghost_fwd_supported(int N, int H, int W, int K, int C);
+int dl3p_ghost_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const float* w1,
+                   const float* s1, const float* h1, int act1, const float* wdw, float* y, int ldy, int N, int H, int W, int K,
+                   int C, void* stream);
+
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP
  * events (hipExtLaunchKernelGGL start/stop events on the launch stream) stored in slot i (0 <= i < 4096);

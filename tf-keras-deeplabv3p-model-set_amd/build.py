@@ -16,7 +16,8 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off']
 # the fused inverted-residual kernels are bound by vector-instruction issue: MFMA results straight into VGPRs (no v_accvgpr_read per
 # result register)
-EXTRA = {'irb_fwd.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'irb_bwd.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+EXTRA = {'irb_fwd.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'irb_bwd.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
+         'ghost_fwd.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
 
 
 def _sources():

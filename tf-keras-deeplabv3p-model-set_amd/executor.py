@@ -18,9 +18,15 @@ import numpy as np
 import torch
 
 from ._lib import lib
-from .graph import ACT_NONE
+from .graph import ACT_NONE, ACT_RELU
 
 MAX_ROWS = 2048
+# The fused ghost-module forward (Executor._find_ghost) has NOT been measured against the pair of launches it replaces
+# (scripts/bench_ghost.py is the measurement; docs/experiments.md), so it is opt-in: DL3P_GHOST=1 fuses the module shapes the
+# kernel was built for, from GHOST_MIN_ROWS pixels per batch (N*H*W) up.  A measured table turns this into the default rule.
+GHOST_ON_BY_DEFAULT = False
+GHOST_DEFAULT = {(16, 8), (16, 24), (48, 12), (24, 36), (72, 12)}
+GHOST_MIN_ROWS = 0
 
 
 def split_gemm_enabled():
@@ -441,6 +447,7 @@ class Executor:
         self._pinned_irb = tuple(self.L.irb_get_plan(i) for i in range(4))
         self._find_irb()
         self._find_up()
+        self._find_ghost()
         self._alloc()
         # tracing runs every kernel once on zero inputs: keep the weights / optimiser state intact
         snap_p, snap_v, snap_step, snap_ostep = store.P.clone(), store.V.clone(), store.step.clone(), store.opt_step.clone()
@@ -646,6 +653,71 @@ class Executor:
             rec = (e, b, d)
             self._irb_expand[e], self._irb_bn[b], self._irb_dw[d] = rec, rec, rec
             self._irb_tensors.add(e.out.id)
+
+    def _find_ghost(self):
+        """GhostModule (deeplabv3p_ghostnet.py:135-153): primary 1x1 conv -> BatchNorm [-> ReLU] -> cheap 3x3 depthwise conv, the two
+        raw outputs the halves [0, c) and [c, 2c) of one Concatenate buffer.  Where both BatchNorms run on inference coefficients
+        (an inference executor, or both layers frozen in a training one) the pair is ONE dl3p_ghost_fwd launch (csrc/ghost_fwd.hip):
+        z1 is stored and, in registers, fed to the depthwise conv instead of being read back.  The launch leaves exactly the
+        tensors the pair leaves, so backward, taps and the weight gradients of non-frozen neighbours do not change.
+        self._ghost_pw / _ghost_dw: the two conv ops of a fused module -> (primary, bn op, cheap).  DL3P_GHOST=1 | 0 switches it
+        (GHOST_ON_BY_DEFAULT where unset); DL3P_GHOST_MIN_ROWS overrides the row threshold AND the shape table GHOST_DEFAULT
+        (DESIGN 4k)."""
+        self._ghost_pw, self._ghost_dw = {}, {}
+        if self.bf16 or os.environ.get('DL3P_GHOST', '1' if GHOST_ON_BY_DEFAULT else '0') == '0':
+            return
+        g, N, L = self.g, self.N, self.L
+        pinned = 'DL3P_GHOST_MIN_ROWS' in os.environ
+        min_rows = int(os.environ['DL3P_GHOST_MIN_ROWS']) if pinned else GHOST_MIN_ROWS
+        index = {id(op): i for i, op in enumerate(g.ops)}
+        readers = {}
+        for op in g.ops:
+            for slot in ('x', 'r', 's'):
+                v = getattr(op, slot, None)
+                if v is not None:
+                    readers.setdefault(v.tensor.root.id, []).append((op, slot, v))
+        bn_ops = {id(op.bn): op for op in g.ops if op.kind == 'bn'}
+        views = {t.id for (t, _, _) in g.act_views.values()}
+        for e in g.ops:
+            if e.kind != 'conv_pw' or e.b is not None or e.bn is None or e.out.base is None or e.out.c0 != 0:
+                continue
+            root, c = e.out.base, e.out.C
+            if root is self.head.tensor or e.cout != c or root.C != 2 * c or root.id in views or e.out.id in views:
+                continue
+            rd = readers.get(root.id, [])
+            dws = [(o, v) for o, slot, v in rd if v.tensor is e.out]
+            if len(dws) != 1 or dws[0][0].kind != 'conv_dw':
+                continue
+            d, v = dws[0]
+            # every other reader takes the whole buffer (the Concatenate's consumers), after the cheap conv has written its half
+            if any(not (o is d or (rv.tensor is root and index[id(o)] > index[id(d)])) for o, slot, rv in rd):
+                continue
+            if (d.k, d.stride, d.rate, d.pad_t, d.pad_l) != (3, 1, 1, 1, 1) or d.bn is None or d.c != c:
+                continue
+            if d.out.base is not root or d.out.c0 != c or d.out.C != c or d in self._up_conv:
+                continue
+            bn = e.bn
+            if (v.bn is not bn or v.group is not bn.group or v.goff != bn.offset or v.act != bn.act
+                    or bn.act not in (ACT_NONE, ACT_RELU) or getattr(v, 'view_grad', None) is not None):
+                continue
+            if self.training and (bn.layer.trainable or d.bn.layer.trainable):
+                continue                    # (batch statistics of z1 would need a pass of their own: DESIGN 4k)
+            b = bn_ops.get(id(bn))
+            if b is None or not index[id(e)] < index[id(b)] < index[id(d)]:
+                continue
+            xt = e.x.tensor
+            if (xt.H, xt.W) != (e.Ho, e.Wo) or (d.Ho, d.Wo) != (e.Ho, e.Wo) or xt.ld % 4 or root.ld % 4:
+                continue
+            if not L.ghost_fwd_supported(N, xt.H, xt.W, e.cin, c):
+                continue
+            if N * xt.H * xt.W < min_rows or not (pinned or (e.cin, c) in GHOST_DEFAULT):
+                continue
+            rec = (e, b, d)
+            self._ghost_pw[e], self._ghost_dw[d] = rec, rec
+
+    def ghost_launches(self):
+        """number of dl3p_ghost_fwd launches in the traced forward (tests, scripts/bench_ghost.py)"""
+        return sum(1 for name, _ in self.fwd.labels if name == 'dl3p_ghost_fwd')
 
     def _find_up(self):
         """Decoder_block (layers.py:207-215): img_resize -> Concatenate([x, skip]) -> 3x3 depthwise conv.  Where the resized tensor's
@@ -872,7 +944,16 @@ class Executor:
                 part = self.partials.data_ptr() if want_stats else None
                 rows = ctypes.c_int(0)
                 xt = op.x.tensor
-                if op in self._irb_expand:
+                if op in self._ghost_pw:
+                    pass                    # (written by the fused launch at the module's depthwise op: _find_ghost)
+                elif op in self._ghost_dw:
+                    e, b, d = self._ghost_dw[op]
+                    exp, eldx, esp, ehp, eact = self.vargs(e.x)
+                    gb = e.bn
+                    P.k(L.ghost_fwd, exp, eldx, esp, ehp, eact, st.ptr(e.w), self.gscale[gb.group.id].data_ptr() + 4 * gb.offset,
+                        self.gshift[gb.group.id].data_ptr() + 4 * gb.offset, gb.act, st.ptr(op.w), self.tptr(e.out), e.out.ld,
+                        N, xt.H, xt.W, e.cin, e.cout, tag=op.name)
+                elif op in self._irb_expand:
                     # fused block: the expand output is never formed.  Its BatchNorm's statistics come from the covariance of the
                     # block INPUT (z = x W is linear): one pass over the K-channel tensor, finalised at the 'bn' op
                     if want_stats:
@@ -1077,6 +1158,8 @@ class Executor:
         # its depthwise op)
         if op in self._irb_dw and self._reads_pending_value(self._irb_dw[op][0].x, groups):
             return True
+        if op in self._ghost_dw and self._reads_pending_value(self._ghost_dw[op][0].x, groups):
+            return True                     # (a fused ghost module reads its input at the depthwise op)
         for slot in ('x', 'r', 's'):
             v = getattr(op, slot, None)
             if v is not None and v.group is not None and id(v.group) in groups:

@@ -52,6 +52,12 @@ def _register_optional():
         deeplab_model_map['peleenet_lite'] = Deeplabv3pLitePeleeNet
     except ImportError:
         pass
+    try:
+        from .ghostnet import Deeplabv3pGhostNet, Deeplabv3pLiteGhostNet
+        deeplab_model_map['ghostnet'] = Deeplabv3pGhostNet
+        deeplab_model_map['ghostnet_lite'] = Deeplabv3pLiteGhostNet
+    except ImportError:
+        pass
 
 
 _register_optional()

@@ -1150,6 +1150,24 @@ def irb_fwd(x, w1, bn_scale, bn_shift, bn_act, wdw, stride=1, padding='same', in
     return (y, rows.value) if partials is not None else y
 
 
+def ghost_fwd_supported(x_shape, C):
+    N, H, W, K = x_shape
+    return bool(lib().ghost_fwd_supported(N, H, W, K, C))
+
+
+def ghost_fwd(x, w1, s1, h1, act1, wdw, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None):
+    """fused ghost module: x (N,H,W,K); w1 (K,C); s1, h1 (C,); wdw (3,3,C) -> y (N,H,W,2C): the raw primary conv output in
+    [0, C), the raw 3x3 depthwise output of act1(z1 * s1 + h1) in [C, 2C); `out`: a (view of a) buffer to write into"""
+    N, H, W, K = x.shape
+    C = w1.shape[-1]
+    y = out if out is not None else torch.empty((N, H, W, 2 * C), dtype=torch.float32, device=x.device)
+    xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
+    lib().ghost_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(w1), _p(s1), _p(h1), act1, _p(wdw), yp, ldy, N, H, W, K, C,
+                    _stream())
+    return y
+
+
 def irb_bwd_sums(x, w1, bn, bn_act, wdw, dy, stride=1, padding='same', in_scale=None, in_shift=None, in_act=ACT_NONE):
     """pass A -> (depthwise kernel gradient (3,3,C), BatchNorm-backward sums float64 [2][C])"""
     N, H, W, K = x.shape
