@@ -820,6 +820,33 @@ int dl3p_ghost_fwd(const float* x, int ldx, const float* in_scale, const float* 
                    const float* s1, const float* h1, int act1, const float* wdw, float* y, int ldy, int N, int H, int W, int K,
                    int C, void* stream);
 
+/* ---------------------------------------------------------------- 2x2 stride-2 transposed convolution (csrc/deconv.hip)
+ * replaces Conv2DTranspose(filters, 2, strides=(2, 2)) (+ bias) of the U-Net up-path, unet/models/unet.py:47,53,59,65 (unet_standard)
+ * and :116-134 (unet_lite).  With k == stride == 2 and no padding every output pixel has exactly one tap, so the operator is the GEMM
+ * X[M][Cin] . W[Cin][4 Cout], M = N H W, whose row m = (n, y, x) and column block (dy, dx) land on output pixel (n, 2y+dy, 2x+dx).
+ *   x  [N][H][W][ldx]   (Cin channels read),  y / dy [N][2H][2W][ldy] (Cout channels), w / gw: the Keras kernel AS STORED,
+ *   (2, 2, Cout, Cin) -- filters before input channels, no flip;  bias / gb [Cout] (or NULL).
+ * Cin, Cout, ldx, ldy multiples of 4, pointers 16-byte aligned, every operand below 4 GiB (32-bit byte offsets in the kernels):
+ * anything else returns DL3P_EINVAL before any launch.  dl3p_deconv2x2_supported: 1 for Cin % 4 == 0 and Cout % 4 == 0.
+ *   fwd:        y[n,2y+dy,2x+dx,co] = sum_ci act(x[n,y,x,ci] * scale + shift) * w[dy][dx][co][ci] + bias[co]; x and y may be channel
+ *               slices of wider buffers; nothing outside the Cout channels of y is touched.  No statistics epilogue.
+ *   bwd_data:   gx[m][ci] (+)= sum_{dy,dx,co} dY[n,2y+dy,2x+dx,co] * w[dy][dx][co][ci] (gradient w.r.t. act(x * scale + shift)).
+ *   bwd_weight: gw[dy][dx][co][ci] = sum_m act(x[m][ci] * scale + shift) * dY[pixel(m,dy,dx)][co]; gb[co] = sum of dY over all 4 M
+ *               output pixels (gb may be NULL).  Slices of M leave slabs in `workspace` (dl3p_deconv2x2_bwd_weight_workspace bytes,
+ *               16-byte aligned) that are added in slice order: no atomics, bitwise repeatable. */
+int dl3p_deconv2x2_supported(int Cin, int Cout);
+/* launch-plan knob of the forward / data-gradient kernel: at most `max_workgroups` persistent workgroups along M (0 = default, two per
+ * CU); tests use it to give every workgroup several row tiles at small sizes. */
+int dl3p_deconv2x2_set_plan(int max_workgroups);
+int dl3p_deconv2x2_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const float* w,
+                       const float* bias, float* y, int ldy, int N, int H, int W, int Cin, int Cout, void* stream);
+int dl3p_deconv2x2_bwd_data(const float* dy, int lddy, const float* w, float* gx, int ldgx, int accumulate, int N, int H, int W,
+                            int Cin, int Cout, void* stream);
+size_t dl3p_deconv2x2_bwd_weight_workspace(int N, int H, int W, int Cin, int Cout);
+int dl3p_deconv2x2_bwd_weight(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const float* dy,
+                              int lddy, float* gw, float* gb, float* workspace, size_t workspace_bytes, int N, int H, int W,
+                              int Cin, int Cout, void* stream);
+
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP
  * events (hipExtLaunchKernelGGL start/stop events on the launch stream) stored in slot i (0 <= i < 4096);

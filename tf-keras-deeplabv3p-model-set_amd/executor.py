@@ -544,6 +544,8 @@ class Executor:
                     ws = max(ws, L.conv2d_gemm_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout, op.k))
                 if self._narrow(op):
                     ws = max(ws, L.conv_narrow_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout))
+            elif op.kind == 'conv_deconv':
+                ws = max(ws, L.deconv2x2_bwd_weight_workspace(N, op.x.tensor.H, op.x.tensor.W, op.cin, op.cout))
         self.workspace = torch.zeros(ws // 4 + 4, **self.f32) if self.training else None
         # slabs of the split-K forward GEMMs (dl3p_pwconv_fwd_wt_splitk), training and inference
         sk = 0 if self.bf16 else max([L.pwconv_fwd_splitk_workspace(N * op.Ho * op.Wo, op.cin, op.cout)
@@ -864,7 +866,7 @@ class Executor:
                 t.root.requires_grad = True
         for op in self.g.ops:
             k = op.kind
-            if k in ('conv_pw', 'conv_dense', 'conv_dw'):
+            if k in ('conv_pw', 'conv_dense', 'conv_dw', 'conv_deconv'):
                 setrg(op.out, op.layer.trainable or rg(op.x))
                 if k == 'conv_dense':
                     setrg(op.col, rg(op.x))
@@ -1019,6 +1021,18 @@ class Executor:
                         st.ptr(op.b) if op.b else None, self.tptr(op.out), op.out.ld, part, ctypes.byref(rows),
                         N * op.Ho * op.Wo, op.kp, op.cout)
                 op.rows = rows.value
+            elif k == 'conv_deconv':
+                # Conv2DTranspose(filters, 2, strides=(2, 2)) + bias: one GEMM whose epilogue scatters the four quadrants (csrc/deconv.hip)
+                assert not self.bf16, 'dl3p_deconv2x2_* has no bf16 twin (model._NO_BF16_TRAINING refuses the U-Net types)'
+                xp, ldx, sp, hp, act = self.vargs(op.x)
+                xt = op.x.tensor
+                P.k(L.deconv2x2_fwd, xp, ldx, sp, hp, act, st.ptr(op.w), st.ptr(op.b) if op.b else None, self.tptr(op.out),
+                    op.out.ld, N, xt.H, xt.W, op.cin, op.cout, tag=op.name)
+            elif k == 'pad_channels':
+                # zero-padded copy (a 1 x 1 im2col whose rows are padded to the wider tensor); no gradient
+                xt, t = op.x.tensor, op.out
+                P.k(L.im2col, self.tptr(xt), xt.ld, None, None, ACT_NONE, self.tptr(t), t.ld, N, xt.H, xt.W, xt.C, 1, 1, 1, 0, 0,
+                    xt.H, xt.W)
             elif k == 'bn':
                 self._bn_forward(P, op)
             elif k == 'materialize':
@@ -1212,8 +1226,10 @@ class Executor:
         vt = getattr(v, 'view_grad', None)
         if vt is not None:
             # bare activation of a materialised tensor: consumers write d/d(act(T)) here; folded into T's
-            # gradient (g * act'(T)) when backward reaches T's producer
-            self._pending_views.setdefault(v.tensor.id, []).append((v.tensor, v.act, vt))
+            # gradient (g * act'(T)) when backward reaches T's producer.  (view_parts: a BatchNorm-free Concatenate, one view
+            # buffer over all branches -- each branch's slice is folded at that branch's producer; graph.concat_act)
+            for tt, act, pv in getattr(v, 'view_parts', None) or [(v.tensor, v.act, vt)]:
+                self._pending_views.setdefault(tt.id, []).append((tt, act, pv))
             return self.tptr(vt, grad=True), vt.ld, vt
         # a Concatenate value carries the activation of its branches: each branch's BatchNormalization
         # backward applies act' to its own channel slice, so the buffer itself takes the plain gradient
@@ -1539,6 +1555,16 @@ class Executor:
                             N * op.Ho * op.Wo, op.kp, op.cout)
                         P.k(L.col2im, self.tptr(op.col, True), op.col.ld, gp, ldg, acc, N, xt.H, xt.W, op.cin, op.k,
                             op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
+            elif k == 'conv_deconv':
+                xp, ldx, sp, hp, act = self.vargs(op.x)
+                xt = op.x.tensor
+                dz, lddz = self.tptr(out, True), out.ld
+                if op.layer.trainable:
+                    wgrad(L.deconv2x2_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, st.ptr(op.w, G), st.ptr(op.b, G) if op.b else None,
+                          ws, wsb, N, xt.H, xt.W, op.cin, op.cout)
+                if xt.requires_grad or xt.root.requires_grad:
+                    gp, ldg, keyt = self._gbuf(op.x)
+                    P.k(L.deconv2x2_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, self._acc(keyt), N, xt.H, xt.W, op.cin, op.cout)
             elif k == 'materialize':
                 gt, ldt = self.tptr(out, True), out.ld
                 M = N * out.H * out.W

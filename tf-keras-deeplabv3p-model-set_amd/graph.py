@@ -147,6 +147,9 @@ class Value:
     def __init__(self, tensor, group=None, goff=0, act=ACT_NONE, bn=None, klayer=None):
         self.tensor, self.group, self.goff, self.act, self.bn = tensor, group, goff, act, bn
         self.klayer = klayer      # the Keras layer this tensor is the output of
+        # channels the Keras tensor has when the device tensor carries zero pad channels behind them (None: all of them);
+        # a conv that reads the value sizes its Keras kernel by this and its device kernel by the tensor (zero pad rows)
+        self.channels = None
 
     def from_layer(self, layer):
         """the same lazy value as the output tensor of another Keras layer (a copy: `self` may have other consumers)"""
@@ -158,6 +161,10 @@ class Value:
     @property
     def shape(self):
         return (self.tensor.H, self.tensor.W, self.tensor.C)
+
+    @property
+    def logical_c(self):
+        return self.tensor.C if self.channels is None else self.channels
 
     @property
     def is_plain(self):
@@ -217,7 +224,8 @@ class GraphBuilder:
             base = {'ReLU': 're_lu', 'Add': 'add', 'Concatenate': 'concatenate', 'Dropout': 'dropout',
                     'ZeroPadding2D': 'zero_padding2d', 'AveragePooling2D': 'average_pooling2d',
                     'Activation': 'activation', 'Multiply': 'multiply', 'Reshape': 'reshape',
-                    'GlobalAveragePooling2D': 'global_average_pooling2d', 'MaxPooling2D': 'max_pooling2d'}.get(kind, kind.lower())
+                    'GlobalAveragePooling2D': 'global_average_pooling2d', 'MaxPooling2D': 'max_pooling2d',
+                    'Conv2DTranspose': 'conv2d_transpose', 'SeparableConv2D': 'separable_conv2d'}.get(kind, kind.lower())
             n = sum(1 for l in self.layers if l.kind == kind and l.name.startswith(base))
             name = base if n == 0 else '%s_%d' % (base, n)
         assert name not in self.layer_by_name, 'duplicate layer name ' + name
@@ -246,27 +254,31 @@ class GraphBuilder:
 
     # ---- Keras layers -----------------------------------------------------------------
     def conv2d(self, x, filters, k, name, stride=1, rate=1, padding='same', use_bias=False, out=None,
-               pad_to=None, kernel_initializer='glorot_uniform'):
+               pad_to=None, kernel_initializer='glorot_uniform', l2=L2_FACTOR, activation=None):
         """DeeplabConv2D (reference layers.py:14-21): glorot_uniform kernel (he_normal in the ResNet50 backbone), zero
-        bias, l2(2e-5) on both"""
+        bias, l2(2e-5) on both.  l2 = 0: a plain Keras Conv2D (the U-Net family); activation: the layer's own
+        `activation=` argument (no Keras layer of its own)"""
         H, W, cin = x.shape
+        cin_keras = x.logical_c
+        assert k == 1 or cin_keras == cin, 'a dense conv reads no channel-padded tensor: ' + str(name)
         src = x
         if not isinstance(padding, str):
             src = self.add_layer(None, 'ZeroPadding2D', inbound=[x])
         Ho, Wo, pt, pl = conv_geometry(H, W, k, stride, rate, padding)
         layer = self.add_layer(name, 'Conv2D', (Ho, Wo, filters), inbound=[src])
+        name = layer.name
         cdev = pad_to or filters
         # dense (k > 1) kernels are stored as the im2col GEMM operand [k*k*cin padded to a multiple of 4][cout]
         kp = (k * k * cin + self.align - 1) // self.align * self.align
         dev_shape = (k, k, cin, cdev) if k == 1 else (kp, cdev)
         if kernel_initializer == 'he_normal':
-            init = lambda s: he_normal(self.rng, s, k * k * cin)
+            init = lambda s: he_normal(self.rng, s, k * k * cin_keras)
         else:
-            init = lambda s: glorot_uniform(self.rng, s, k * k * cin, k * k * filters)
-        wp = layer.add_param('kernel', (k, k, cin, filters), init, l2=L2_FACTOR, dev_shape=dev_shape)
+            init = lambda s: glorot_uniform(self.rng, s, k * k * cin_keras, k * k * filters)
+        wp = layer.add_param('kernel', (k, k, cin_keras, filters), init, l2=l2, dev_shape=dev_shape)
         bp = None
         if use_bias:
-            bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=L2_FACTOR,
+            bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=l2,
                                  dev_shape=(cdev,))
         if out is None:
             out = self.new_tensor(Ho, Wo, cdev, name)
@@ -277,7 +289,66 @@ class GraphBuilder:
         col = self.new_tensor(Ho, Wo, kp, name + '_im2col') if kind == 'conv_dense' else None
         self.ops.append(Op(kind, name=name, layer=layer, x=x, w=wp, b=bp, out=out, k=k, stride=stride, rate=rate,
                            pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo, cin=cin, cout=cdev, bn=None, col=col, kp=kp))
-        return Value(out, klayer=layer)
+        y = Value(out, klayer=layer)
+        if cdev != filters:
+            y.channels = filters
+        return y if activation is None else self.activation(y, activation, layer=layer)
+
+    def separable_conv2d(self, x, filters, name, activation=None, out=None, pad_to=None):
+        """SeparableConv2D(filters, 3, padding='same') (reference unet/models/unet.py:97-138): ONE Keras layer with three weights,
+        depthwise_kernel (3,3,Cin,1), pointwise_kernel (1,1,Cin,filters), bias -- a 3x3 depthwise conv and a 1x1 conv with
+        no bias and no activation between them.  Plain Keras layer: no regulariser.  Both kernels keep Keras' default
+        glorot_uniform (the layer's kernel_initializer argument reaches neither; DESIGN 4l, unpinned)."""
+        H, W, c = x.shape
+        ck = x.logical_c
+        layer = self.add_layer(name, 'SeparableConv2D', (H, W, filters), inbound=[x])
+        name = layer.name
+        cdev = pad_to or filters
+        dwp = layer.add_param('depthwise_kernel', (3, 3, ck, 1), lambda s: glorot_uniform(self.rng, s, 9 * ck, 9),
+                              l2=0.0, dev_shape=(3, 3, c, 1))
+        pwp = layer.add_param('pointwise_kernel', (1, 1, ck, filters), lambda s: glorot_uniform(self.rng, s, ck, filters),
+                              l2=0.0, dev_shape=(1, 1, c, cdev))
+        bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=0.0, dev_shape=(cdev,))
+        mid = self.new_tensor(H, W, c, name + '_depthwise')
+        self.ops.append(Op('conv_dw', name=name + '_depthwise', layer=layer, x=x, w=dwp, out=mid, k=3, stride=1, rate=1,
+                           pad_t=1, pad_l=1, Ho=H, Wo=W, c=c, bn=None))
+        if out is None:
+            out = self.new_tensor(H, W, cdev, name)
+        assert (out.H, out.W, out.C) == (H, W, cdev), (name, (out.H, out.W, out.C), (H, W, cdev))
+        self.ops.append(Op('conv_pw', name=name, layer=layer, x=Value(mid, klayer=layer), w=pwp, b=bp, out=out, k=1, stride=1,
+                           rate=1, pad_t=0, pad_l=0, Ho=H, Wo=W, cin=c, cout=cdev, bn=None, col=None, kp=c))
+        y = Value(out, klayer=layer)
+        if cdev != filters:
+            y.channels = filters
+        return y if activation is None else self.activation(y, activation, layer=layer)
+
+    def conv2d_transpose(self, x, filters, name, use_bias=True, out=None, activation=None):
+        """Conv2DTranspose(filters, 2, strides=(2, 2)) (reference unet/models/unet.py:47,53,59,65): he_normal kernel stored
+        (2, 2, filters, Cin) -- Keras takes the fans from that shape, so fan_in = 4 filters -- zero bias, no regulariser.  The
+        result is a raw tensor of twice the size with a lazy activation, like any conv output (csrc/deconv.hip)."""
+        H, W, cin = x.shape
+        assert x.logical_c == cin and cin % 4 == 0 and filters % 4 == 0, 'conv2d_transpose: channels must be multiples of 4'
+        layer = self.add_layer(name, 'Conv2DTranspose', (2 * H, 2 * W, filters), inbound=[x])
+        name = layer.name
+        wp = layer.add_param('kernel', (2, 2, filters, cin), lambda s: he_normal(self.rng, s, 4 * filters), l2=0.0)
+        bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=0.0) if use_bias else None
+        if out is None:
+            out = self.new_tensor(2 * H, 2 * W, filters, name)
+        assert (out.H, out.W, out.C) == (2 * H, 2 * W, filters), (name, (out.H, out.W, out.C))
+        self.ops.append(Op('conv_deconv', name=name, layer=layer, x=x, w=wp, b=bp, out=out, cin=cin, cout=filters, bn=None))
+        y = Value(out, klayer=layer)
+        return y if activation is None else self.activation(y, activation, layer=layer)
+
+    def pad_channels(self, x, C):
+        """a zero-padded device copy of a materialised tensor with C >= its channels (the 3-channel image in front of a depthwise
+        conv, whose kernels need C % 4 == 0): one small launch, no gradient, no Keras layer"""
+        H, W, c = x.shape
+        assert x.is_plain and c <= C
+        out = self.new_tensor(H, W, C, 'pad%d_%s' % (C, x.tensor.name))
+        self.ops.append(Op('pad_channels', name=out.name, x=x, out=out))
+        y = Value(out, klayer=x.klayer)
+        y.channels = x.logical_c
+        return y
 
     def dwconv2d(self, x, k, name, stride=1, rate=1, padding='same', out=None):
         """DeeplabDepthwiseConv2D (reference layers.py:24-31); its kernel_regularizer never reaches the
@@ -326,8 +397,15 @@ class GraphBuilder:
                 return op
         return None
 
-    def activation(self, v, act, name=None, kind='ReLU'):
-        layer = self.add_layer(name, kind, v.shape, inbound=[v])
+    def activation(self, v, act, name=None, kind='ReLU', layer=None):
+        """layer: the Keras layer whose own `activation=` argument this is (Conv2D(..., activation='relu')): no layer is added"""
+        out = self._activation(v, act, name, kind, layer)
+        out.channels = v.channels
+        return out
+
+    def _activation(self, v, act, name, kind, layer):
+        if layer is None:
+            layer = self.add_layer(name, kind, v.shape, inbound=[v])
         if act == ACT_HSWISH:
             # hard_swish(x) = Multiply()([Activation(hard_sigmoid)(x), x]) (deeplabv3p_mobilenetv3.py:102-103): two Keras layers
             layer = self.add_layer(None, 'Multiply', v.shape, inbound=[layer, v])
@@ -378,9 +456,9 @@ class GraphBuilder:
         layer = self.add_layer(name, 'Add', a.shape, inbound=keras_inputs or [a, b])
         return self.materialize(b, residual=a, name=name).from_layer(layer)
 
-    def dropout(self, v, rate, name=None):
+    def dropout(self, v, rate, name=None, out=None):
         layer = self.add_layer(name, 'Dropout', v.shape, inbound=[v])
-        return self.materialize(v, dropout=rate, name=name).from_layer(layer)
+        return self.materialize(v, dropout=rate, name=name, out=out).from_layer(layer)
 
     def se_multiply(self, x, s, name=None):
         """Multiply([x, s]) with s (1,1,C) broadcast over the pixels (reference deeplabv3p_mobilenetv3.py:145)"""
@@ -454,6 +532,33 @@ class GraphBuilder:
             slices.append((base.slice(off, c), off))
             off += c
         return base, slices, group
+
+    def concat_buffer_act(self, H, W, channels, name, act):
+        """a Concatenate target whose branches carry a bare activation and NO BatchNormalization (the U-Net merges): the raw
+        conv outputs are written into the slices, every reader applies `act` in its prologue, and the gradient of the
+        activated tensor is collected in ONE view buffer of the same width -- the consumer of the concatenation writes all of
+        it, a reader of a single branch (the max-pool beside a skip connection) adds into its slice -- that backward folds
+        into each branch's own gradient as g * act'(T) when it reaches the branch's producer.  -> (base, slices)"""
+        base = self.new_tensor(H, W, sum(channels), name)
+        vb = self.new_tensor(H, W, sum(channels), 'actview%d_%s' % (act, name))
+        vb.grad_only = True
+        slices, off = [], 0
+        for c in channels:
+            t = base.slice(off, c)
+            self.act_views[(t.id, act)] = (t, act, vb.slice(off, c))
+            slices.append(t)
+            off += c
+        base.act_view = (act, vb, slices)
+        return base, slices
+
+    def concat_act(self, base, inputs, name=None):
+        """concatenate(inputs) over a concat_buffer_act target, inputs in the reference's argument order"""
+        act, vb, slices = base.act_view
+        layer = self.add_layer(name, 'Concatenate', (base.H, base.W, base.C), inbound=inputs)
+        out = Value(base, None, 0, act, None, klayer=layer)
+        out.view_grad = vb
+        out.view_parts = [self.act_views[(t.id, act)] for t in slices]
+        return out
 
     def concat_value(self, base, group, act, inputs, name=None):
         """`inputs`: the branch values in the order of the reference's Concatenate([...]) call"""

@@ -978,8 +978,9 @@ DeeplabModel.evaluate_miou = _evaluate_miou
 # model types whose graphs contain ops without a bf16 kernel on the TRAINING path are rejected when the model is built, not at
 # the first train step.  Empty since round 3: the data gradient of a dense k x k conv (dl3p_col2im_bf16 behind the
 # GEMM) and max pooling (dl3p_maxpool2d_*_bf16) closed the gap for Xception and ResNet50 -- train.py:37-46 applies the policy to
-# every model type.
-_NO_BF16_TRAINING = {}
+# every model type.  The U-Net types (get_unet_model) are refused under the policy whether built for training or not: the 2x2
+# stride-2 transposed conv (csrc/deconv.hip) has no bf16 twin yet.
+_NO_BF16_TRAINING = {'unet_standard': 'dl3p_deconv2x2_* has no bf16 kernels', 'unet_lite': 'dl3p_deconv2x2_* has no bf16 kernels'}
 
 
 def get_deeplabv3p_model(model_type, num_classes, model_input_shape, output_stride, freeze_level=0,
@@ -1060,6 +1061,46 @@ def _build_model(model_type, num_classes, model_input_shape, output_stride, free
         for i in range(len(model.layers)):
             model.layers[i].trainable = True
         print('Unfreeze all of the layers.')
+    return model
+
+
+def get_unet_model(model_type, num_classes, model_input_shape, freeze_level=0, weights_path=None, training=True, seed=0):
+    """unet/model.py:21-61, same positional arguments (+ `seed`, weight initialisation): 'unet_standard' | 'unet_lite' with the
+    reference's head -- the final Conv2D(num_classes, 1) logits are already at full resolution -- [Reshape] -> Softmax('pred_mask').
+    freeze_level is accepted and ignored like there (its code is commented out, :50-59): every layer is trainable.  The
+    returned model is a DeeplabModel: compile / fit / predict / evaluate_miou / save / load_weights as for the DeepLab types."""
+    from . import mixed_precision, unet as unet_mod
+    if model_type not in unet_mod.unet_model_map.keys():
+        raise ValueError('This model type is not supported now')
+    if model_type == 'unet_simple':
+        raise ValueError('unet_simple is not built: it needs ' + ', '.join(unet_mod.UNET_SIMPLE_MISSING))
+    if not 1 <= int(num_classes) <= 253:
+        raise ValueError('num_classes must be in [1, 253] (got %r)' % (num_classes,))
+    H, W = model_input_shape
+    if H % 16 or W % 16:
+        # four 2x2 poolings and four 2x upsamplings: Keras fails at the first `concatenate` otherwise
+        raise ValueError('U-Net input height and width must be multiples of 16 (got %r)' % ((H, W),))
+    if mixed_precision.is_bf16() and model_type in _NO_BF16_TRAINING:
+        raise ValueError("model type '%s' is not built for the mixed_bfloat16 policy (%s); build it under the float32 policy"
+                         % (model_type, _NO_BF16_TRAINING[model_type]))
+    g, x = unet_mod.unet_model_map[model_type](num_classes, input_shape=(H, W, 3), weights=None, seed=seed)
+    base_len = len(g.layers)
+    # the classifier: a plain Conv2D(num_classes, 1, padding='same') -- glorot_uniform, zero bias, no regulariser -- reading the
+    # 2 logical channels of the padded bottleneck; its class dimension is padded to a multiple of 4 like conv_upsample's
+    cpad = (num_classes + g.align - 1) // g.align * g.align
+    x = g.conv2d(x, num_classes, 1, None, use_bias=True, pad_to=cpad, l2=0.0)
+    out = x
+    if training:
+        out = g.passthrough(out, 'Reshape', (H * W, num_classes))
+    out = g.passthrough(out, 'Softmax', (H * W, num_classes) if training else (H, W, num_classes), name='pred_mask')
+    g.output_layer = out.klayer
+    if x.tensor.C != cpad or not x.is_plain or (x.tensor.H, x.tensor.W) != (H, W):
+        raise AssertionError('head tensor layout')
+    model = DeeplabModel(g, x, model_type, num_classes, (H, W), training, base_len, seed=seed, bf16=False)
+    model.name = model_type
+    if weights_path:
+        model.load_weights(weights_path, by_name=False)
+        print('Load weights {}.'.format(weights_path))
     return model
 
 

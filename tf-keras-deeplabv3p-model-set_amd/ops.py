@@ -1216,3 +1216,46 @@ def irb_bwd_data(x, w1, bn, bn_act, wdw, dy, stride=1, padding='same', in_scale=
     r = rows.value
     gw = slabs[:r * K * C].view(r, K * C).double().sum(0).float().view(K, C)
     return gw, gx, part0, r
+
+
+# ------------------------------------------------------------------------------------- 2x2 stride-2 transposed conv
+def deconv2x2_supported(Cin, Cout):
+    return bool(lib().deconv2x2_supported(Cin, Cout))
+
+
+def deconv2x2_fwd(x, w, bias=None, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None):
+    """x (N,H,W,Cin); w the Keras Conv2DTranspose kernel as stored, (2,2,Cout,Cin) -> y (N,2H,2W,Cout)"""
+    N, H, W, Cin = x.shape
+    Cout = w.shape[2]
+    y = out if out is not None else torch.empty((N, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
+    xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
+    lib().deconv2x2_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, _p(w), _p(bias), yp, ldy, N, H, W, Cin, Cout,
+                        _stream())
+    return y
+
+
+def deconv2x2_bwd_data(dy, w, out=None, accumulate=False):
+    """dy (N,2H,2W,Cout) -> gx (N,H,W,Cin), the gradient w.r.t. the (activated) input of deconv2x2_fwd"""
+    N, H2, W2, Cout = dy.shape
+    Cin = w.shape[3]
+    gx = out if out is not None else torch.empty((N, H2 // 2, W2 // 2, Cin), dtype=torch.float32, device=dy.device)
+    dp, ldd = _pl(dy)
+    gp, ldg = _pl(gx)
+    lib().deconv2x2_bwd_data(dp, ldd, _p(w), gp, ldg, int(accumulate), N, H2 // 2, W2 // 2, Cin, Cout, _stream())
+    return gx
+
+
+def deconv2x2_bwd_weight(x, dy, in_scale=None, in_shift=None, in_act=ACT_NONE, with_bias=False, workspace=None):
+    """-> gw (2,2,Cout,Cin) [, gb (Cout,)]"""
+    N, H, W, Cin = x.shape
+    Cout = dy.shape[-1]
+    need = lib().deconv2x2_bwd_weight_workspace(N, H, W, Cin, Cout)
+    ws = workspace if workspace is not None else torch.empty(max(need, 16) // 4, dtype=torch.float32, device=x.device)
+    gw = torch.empty((2, 2, Cout, Cin), dtype=torch.float32, device=x.device)
+    gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if with_bias else None
+    xp, ldx = _pl(x)
+    dp, ldd = _pl(dy)
+    lib().deconv2x2_bwd_weight(xp, ldx, _p(in_scale), _p(in_shift), in_act, dp, ldd, _p(gw), _p(gb), _p(ws),
+                               ws.numel() * 4, N, H, W, Cin, Cout, _stream())
+    return (gw, gb) if with_bias else gw
