@@ -52,19 +52,20 @@ for (n, H, W, K, C, s) in SHAPES:
     gx = torch.empty((n, H, W, K), device='cuda')
     st = torch.cuda.current_stream().cuda_stream
     P = lambda t: None if t is None else t.data_ptr()
-    cov_rows = torch.empty(256 * (K + K * K), dtype=torch.float64, device='cuda')
+    cov_cap = L.irb_cov_rows_max()
+    cov_rows = torch.empty(cov_cap * (K + K * K), dtype=torch.float64, device='cuda')
     cov_sums = torch.empty(K + K * K, dtype=torch.float64, device='cuda')
     rows = ctypes.c_int(0)
     geo = (n, H, W, K, C, s, pt, pl, Ho, Wo)
     M = n * H * W
 
     def stats():
-        L.irb_cov_stats(P(x), K, P(xs), P(xh), 0, P(cov_rows), ctypes.byref(rows), M, K, st)
+        L.irb_cov_stats(P(x), K, P(xs), P(xh), 0, P(cov_rows), cov_cap, ctypes.byref(rows), M, K, st)
         L.irb_cov_reduce(P(cov_rows), rows.value, K, P(cov_sums), st)
         L.irb_bn_finalize_cov(P(cov_sums), P(w1), K, C, float(M), P(bn.gamma), P(bn.beta), bn.eps, bn.momentum, P(bn.moving_mean),
                               P(bn.moving_var), 1, P(bn.scale), P(bn.shift), P(bn.mean), P(bn.invstd), st)
     t_stats = timed(stats)
-    t_cov = timed(lambda: L.irb_cov_stats(P(x), K, P(xs), P(xh), 0, P(cov_rows), ctypes.byref(rows), M, K, st))
+    t_cov = timed(lambda: L.irb_cov_stats(P(x), K, P(xs), P(xh), 0, P(cov_rows), cov_cap, ctypes.byref(rows), M, K, st))
     head = (P(x), K, P(xs), P(xh), 0, P(w1), P(bn.scale), P(bn.shift), ops.ACT_RELU6)
     res = ['%dx%dx%dx%d->%d s%d' % (n, H, W, K, C, s), 'cov %.1f +reduce+finalize %.1f' % (t_cov, t_stats)]
     for ct in knob('IRB_CT', [1, 2]):

@@ -10,7 +10,7 @@ N = int(os.environ.get('DL3P_ST_N', 16))
 model = pkg.get_deeplabv3p_model(mt, 21, (513, 513), 16, freeze_level=0, training=True)
 model.compile(optimizer=pkg.SGD(0.01, momentum=0.9), loss=pkg.SparseCategoricalCrossEntropy(ignore_index=255))
 ex = model._executor(N, True)
-rec = ex._wgrad_jobs.cpu().numpy().view(np.dtype([('src', '<u8'), ('dst', '<u8'), ('rows', '<i4'), ('n', '<i4')]))
+rec = ex._bt.wgrad_tables[-1][0].cpu().numpy().view(np.dtype([('src', '<u8'), ('dst', '<u8'), ('rows', '<i4'), ('n', '<i4')]))
 G0 = ex.store.G.data_ptr()
 names = {}
 for lay in ex.store.layers if hasattr(ex.store, 'layers') else []:

@@ -11,6 +11,8 @@ between graph segments.
 
 PyTorch only provides memory, streams, graphs and torch.distributed here.
 """
+import collections
+import contextlib
 import ctypes
 import os
 import zlib
@@ -27,6 +29,18 @@ MAX_ROWS = 2048
 GHOST_ON_BY_DEFAULT = False
 GHOST_DEFAULT = {(16, 8), (16, 24), (48, 12), (24, 36), (72, 12)}
 GHOST_MIN_ROWS = 0
+
+CONV_KINDS = ('conv_pw', 'conv_dense', 'conv_dw')
+# the kernel family a conv runs on (Executor._route)
+(R_IRB_EXPAND, R_IRB_DW, R_GHOST_PW, R_GHOST_DW, R_PW, R_DW, R_STEM, R_NARROW, R_GEMM, R_IM2COL) = (
+    'irb_expand', 'irb_dw', 'ghost_pw', 'ghost_dw', 'pw', 'dw', 'stem', 'narrow', 'gemm', 'im2col')
+# the sums-of-the-BatchNorm-in-front group of a data-gradient launch that carries none (Executor._front_sums)
+NO_FRONT_SUMS = (None, 0, None, None, ACT_NONE, None, None, None, None)
+# A BatchNorm-backward apply pass taken over by the conv that produced z (Executor._bn_backward), in the order the C ABI takes it:
+# gradient of the BatchNorm output, z, the BatchNorm's coefficients and activation, its batch statistics and coefficient triple.
+# Folded into the weight gradient; into the DATA gradient (FoldedDg) with where that leaves dz for the weight gradient
+Folded = collections.namedtuple('Folded', 'g ldg z ldz scale shift act mean invstd coef')
+FoldedDg = collections.namedtuple('FoldedDg', Folded._fields + ('dz', 'lddz'))
 
 
 def split_gemm_enabled():
@@ -270,6 +284,15 @@ class Plan:
         self.segments = None
         self.tags = {}
 
+    @contextlib.contextmanager
+    def at(self, label):
+        """the launches recorded inside belong to `label`"""
+        ctx, self.ctx = self.ctx, label
+        try:
+            yield
+        finally:
+            self.ctx = ctx
+
     def k(self, fn, *args, tag=None):
         fn(*args, torch.cuda.current_stream().cuda_stream)
         if tag is not None:
@@ -393,6 +416,39 @@ class Probe:
         return sum(ts) / max(1, len(ts))
 
 
+class BackwardTrace:
+    """what _trace_backward and the methods it dispatches to share while ONE backward plan is traced.  The executor keeps it
+    (Executor._bt): the reduce launches of the plan read wgrad_tables at every replay"""
+
+    def __init__(self):
+        self.written = set()          # ids of the tensors whose gradient buffer has been written (_acc)
+        self.pending_views = {}       # tensor id -> bare-activation views whose gradient is folded in at its producer (_gbuf)
+        self.processed = set()        # the ops the loop has passed
+        self.bn_done = set()          # 'bn' ops whose backward has been issued
+        self.readers = {}             # 'bn' op -> the ops that read its output (_bn_readers)
+        self.bn_of = {}               # id(z tensor) -> 'bn' op
+        self.fuse = {}                # conv -> the 'bn' op in front of it whose backward sums its data gradient carries (_bn_fusion_map)
+        self.fuse_add = {}            # ... through a residual Add (_bn_fusion_through_adds)
+        self.presums = {}             # 'bn' op -> partial rows left in partials2 by such a data gradient
+        self.galias = {}              # z tensor id -> (ptr, ld) of the buffer that already holds d/d(BN(z) output)
+        self.alias_ok = True
+        self.defer = False            # SyncBatchNorm: weight gradients wait in `deferred` for the next all-reduce to hide behind
+        self.deferred = []
+        self.pending = []             # SyncBatchNorm: ('bn' op, staging offset, label) waiting for their all-reduce
+        self.stage_off = 0
+        self.sync_g = {}              # SyncBatchNorm: 'bn' op -> (ptr, ld) its apply reads the gradient from (after the all-reduce)
+        self.batch = False            # weight gradients leave slabs for dl3p_reduce_rows_batched (DL3P_BATCHED_WGRAD)
+        self.batch_wgrad = False      # ... and are issued in line (not deferred)
+        self.folded = {}              # z tensor id -> Folded: the apply pass taken over by the conv's weight gradient
+        self.folded_dg = {}           # z tensor id -> FoldedDg: ... by its DATA gradient (row-stationary split GEMM, pw_split_rs.hip)
+        self.dz_not_kept = set()      # (debug record) z tensors whose gradient buffer still holds d/d(BN output) after backward
+        self.jobs = []                # (slab pointer, destination pointer, rows, n) issued and not yet reduced
+        self.wgrad_tables = []        # the job / block tables of every reduce launch
+        self.ws = self.wsb = 0        # the shared weight-gradient workspace
+        self.slab_ws = self.dz_scratch = None
+        self.slab_off = 0             # floats of slab_ws handed out
+
+
 class Executor:
     def __init__(self, graph, head, store, batch, training, num_classes, ignore_index=255, dist=None,
                  seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
@@ -437,6 +493,7 @@ class Executor:
         self.bf16 = bool(getattr(store, 'bf16', False))
         self.adt = torch.bfloat16 if self.bf16 else torch.float32
         self._sb_used_f, self._sb_used_b = set(), set()      # pointwise convs whose forward / data gradient took the split GEMM
+        self._routes = {}                                    # conv op -> its kernel family (_route)
         # the weight gradients pick the split kernel inside the library (dl3p_pwconv_bwd_weight[_slabs], wgrad_sb_route): the switch
         # is process-wide there, so every executor states its own before it sizes workspaces, traces, or runs eagerly
         self._split_wgrad = int(split_gemm_enabled() and not self.bf16 and os.environ.get('DL3P_SPLIT_WGRAD', '1') not in ('', '0'))
@@ -775,8 +832,7 @@ class Executor:
         e, b, d = rec
         bn = b.bn
         xp, ldx, sp, hp, act = self.vargs(e.x)
-        return (xp, ldx, sp, hp, act, self.store.ptr(e.w), self.gscale[bn.group.id].data_ptr() + 4 * bn.offset,
-                self.gshift[bn.group.id].data_ptr() + 4 * bn.offset, bn.act)
+        return (xp, ldx, sp, hp, act, self.store.ptr(e.w), *self._bn_coeffs(bn), bn.act)
 
     def _stem_direct(self, op):
         """the RGB stem runs as the LDS-staged implicit GEMM (csrc/stem.hip) instead of im2col + GEMM: fp32 path, raw image
@@ -788,29 +844,47 @@ class Executor:
                 and self.L.stem_conv_supported(op.cin, op.cout, op.k, op.stride, op.rate)
                 and os.environ.get('DL3P_STEM_DIRECT', '1') != '0')
 
+    def _route(self, op):
+        """the kernel family a conv runs on, decided once per op in the order the forward tests it: the two halves of a fused ghost
+        module (forward only: _bwd_route) or fused inverted-residual block, then pointwise, depthwise and, for a dense conv, the
+        direct stem, the narrow direct kernels, the implicit GEMM or im2col + GEMM.  Under the bf16 policy none of the fp32-only
+        families is offered, so a dense conv there is on im2col.  Which kernel of the family a launch gets can further depend on
+        its role (_use_sb, _use_sb_dense, the split-K plan): that is asked where the launch is issued"""
+        r = self._routes.get(op)
+        if r is None:
+            r = self._routes[op] = (R_GHOST_PW if op in self._ghost_pw else R_GHOST_DW if op in self._ghost_dw
+                                    else R_IRB_EXPAND if op in self._irb_expand else R_IRB_DW if op in self._irb_dw
+                                    else R_PW if op.kind == 'conv_pw' else R_DW if op.kind == 'conv_dw'
+                                    else R_STEM if self._stem_direct(op) else R_NARROW if self._narrow(op)
+                                    else R_GEMM if self._dense_gemm(op) else R_IM2COL)
+        return r
+
+    def _bwd_route(self, op):
+        """the route of a conv's gradients: a ghost module is fused in the forward only"""
+        return {R_GHOST_PW: R_PW, R_GHOST_DW: R_DW}.get(self._route(op), self._route(op))
+
     def _slab_bytes(self, op):
         """workspace bytes of a conv's weight gradient when it can leave its slabs for the batched reduction (0: it has a bias
         gradient, runs on <= 64 rows, or is a dense conv on the im2col route)"""
         L, N = self.L, self.N
-        if op in self._irb_expand or op in self._irb_dw:
+        r = self._bwd_route(op)
+        if r in (R_IRB_EXPAND, R_IRB_DW):
             e, b, d = self._irb_expand.get(op) or self._irb_dw[op]
             xt = e.x.tensor
             return L.irb_bwd_workspace(1 if op is e else 0, N, xt.H, xt.W, e.cin, e.cout, d.stride, d.pad_t, d.pad_l)
-        if getattr(op, 'b', None) is not None or N * op.Ho * op.Wo <= 64:
+        if getattr(op, 'b', None) is not None or self._rows(op) <= 64:
             return 0
+        if r == R_DW:
+            return (L.dwconv2d_bwd_weight_workspace_bf16 if self.bf16 else L.dwconv2d_bwd_weight_workspace)(N, op.Ho, op.Wo, op.c, op.k)
         if self.bf16:
-            if op.kind == 'conv_dw':
-                return L.dwconv2d_bwd_weight_workspace_bf16(N, op.Ho, op.Wo, op.c, op.k)
-            return L.pwconv_bwd_weight_workspace_bf16(N * op.Ho * op.Wo, op.cin if op.kind == 'conv_pw' else op.kp, op.cout)
-        if op.kind == 'conv_pw':
-            return L.pwconv_bwd_weight_workspace(N * op.Ho * op.Wo, op.cin, op.cout)
-        if op.kind == 'conv_dw':
-            return L.dwconv2d_bwd_weight_workspace(N, op.Ho, op.Wo, op.c, op.k)
-        if self._stem_direct(op):
+            return L.pwconv_bwd_weight_workspace_bf16(*self._mkn(op))
+        if r == R_PW:
+            return L.pwconv_bwd_weight_workspace(*self._mkn(op))
+        if r == R_STEM:
             return L.stem_conv_bwd_weight_workspace(N, op.Ho, op.Wo, op.cout)
-        if self._narrow(op):
+        if r == R_NARROW:
             return L.conv_narrow_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout)
-        if self._dense_gemm(op):
+        if r == R_GEMM:
             return L.conv2d_gemm_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout, op.k)
         return 0
 
@@ -827,8 +901,7 @@ class Executor:
             maps[v].extend((j, b) for b in range((n + be - 1) // be))
         jt = torch.from_numpy(rec.view(np.uint8).copy()).to(self.dev)
         mt = [torch.tensor(m if m else [(0, 0)], dtype=torch.int32, device=self.dev) for m in maps]
-        self._wgrad_tables.append((jt, mt))         # the launches read them at every replay
-        self._wgrad_jobs = jt
+        self._bt.wgrad_tables.append((jt, mt))      # the launches read them at every replay
         P.k(L.reduce_rows_batched, jt.data_ptr(), mt[0].data_ptr(), len(maps[0]), mt[1].data_ptr(), len(maps[1]))
 
     def _narrow(self, op):
@@ -898,6 +971,52 @@ class Executor:
             hp = self.gshift[v.group.id].data_ptr() + 4 * v.goff
         return self.tptr(v.tensor), v.tensor.ld, sp, hp, v.act
 
+    def _rows(self, op):
+        """output pixels of a conv over the batch: the rows of its GEMM"""
+        return self.N * op.Ho * op.Wo
+
+    def _mkn(self, op):
+        """(rows, reduction length, outputs): the tail of the GEMM launches of a pointwise conv, or of a dense one over its im2col matrix"""
+        return self._rows(op), (op.cin if op.kind == 'conv_pw' else op.kp), op.cout
+
+    def _geo(self, op, form):
+        """the geometry tail of a conv's launches.  'dw': one channel count in front of the window (the depthwise kernels; im2col /
+        col2im over a dense conv's Cin), 'dense': Cin, Cout and the window (implicit GEMM), 'stem': the direct stem kernels,
+        'io': image and channel counts only (narrow direct kernels, the 2x2 transposed conv)"""
+        xt = op.x.tensor
+        img = (self.N, xt.H, xt.W)
+        if form == 'io':
+            return img + (op.cin, op.cout)
+        if form == 'stem':
+            return img + (op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo)
+        ch = (op.cin, op.cout) if form == 'dense' else (op.c if op.kind == 'conv_dw' else op.cin,)
+        return img + ch + (op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
+
+    def _bn_coeffs(self, bn):
+        """(scale_ptr, shift_ptr) of a BatchNorm's slice of its group's coefficient vectors"""
+        return self.gscale[bn.group.id].data_ptr() + 4 * bn.offset, self.gshift[bn.group.id].data_ptr() + 4 * bn.offset
+
+    def _front_bn(self, conv):
+        """(front, front_add): the 'bn' op in front of `conv` whose backward sums the conv's data gradient carries -- read by the
+        conv directly, or through a residual Add (at most one of the two; BackwardTrace.fuse / fuse_add)"""
+        front, front_add = (b if b is not None and b.z.requires_grad else None
+                            for b in (self._bt.fuse.get(conv), self._bt.fuse_add.get(conv)))
+        return front, (front_add if front is None else None)
+
+    def _front_sums(self, bn_op, partials, rows):
+        """(z, ld, scale, shift, act, mean, invstd, partials, &rows): what a data gradient needs to leave the backward sums of the
+        BatchNorm `bn_op` in front of its conv as rows.value partial rows of `partials`; NO_FRONT_SUMS without one"""
+        if bn_op is None:
+            return NO_FRONT_SUMS
+        bn = bn_op.bn
+        aux = self.bn_aux[bn]
+        return (self.tptr(bn_op.z), bn_op.z.ld, *self._bn_coeffs(bn), bn.act, aux['mean'].data_ptr(), aux['invstd'].data_ptr(),
+                partials.data_ptr(), ctypes.byref(rows))
+
+    @property
+    def _dz_not_kept(self):
+        return self._bt.dz_not_kept
+
     def view(self, t, grad=False, weights=None):
         """torch view (N,H,W,C) of a graph tensor (test / debug hook).  weights: {parameter name: array} standing in for the
         parameter store where a tensor has to be re-formed (after a training step the store holds the UPDATED kernels; a test that
@@ -938,96 +1057,13 @@ class Executor:
             P.ctx = _op_label(op)
             if self._fwd_pending and k not in ('bn', 'broadcast') and self._reads_pending(op):
                 self._flush_bn_forward(P)
-            if k in ('conv_pw', 'conv_dense', 'conv_dw'):
-                # (the depthwise conv of a fused inverted-residual block reads no buffer of its own: its input is recomputed)
-                xp, ldx, sp, hp, act = self.vargs(op.x) if op not in self._irb_dw else (None, 0, None, None, ACT_NONE)
-                bn = op.bn
-                want_stats = train and bn is not None and bn.layer.trainable
-                part = self.partials.data_ptr() if want_stats else None
-                rows = ctypes.c_int(0)
-                xt = op.x.tensor
-                if op in self._ghost_pw:
-                    pass                    # (written by the fused launch at the module's depthwise op: _find_ghost)
-                elif op in self._ghost_dw:
-                    e, b, d = self._ghost_dw[op]
-                    exp, eldx, esp, ehp, eact = self.vargs(e.x)
-                    gb = e.bn
-                    P.k(L.ghost_fwd, exp, eldx, esp, ehp, eact, st.ptr(e.w), self.gscale[gb.group.id].data_ptr() + 4 * gb.offset,
-                        self.gshift[gb.group.id].data_ptr() + 4 * gb.offset, gb.act, st.ptr(op.w), self.tptr(e.out), e.out.ld,
-                        N, xt.H, xt.W, e.cin, e.cout, tag=op.name)
-                elif op in self._irb_expand:
-                    # fused block: the expand output is never formed.  Its BatchNorm's statistics come from the covariance of the
-                    # block INPUT (z = x W is linear): one pass over the K-channel tensor, finalised at the 'bn' op
-                    if want_stats:
-                        crow = ctypes.c_int(0)
-                        P.k(L.irb_cov_stats, xp, ldx, sp, hp, act, self.irb_cov_rows.data_ptr(), self.irb_cov_cap, ctypes.byref(crow),
-                            N * xt.H * xt.W, op.cin)
-                        if self.sync_bn:
-                            off = self._fwd_stage_off
-                            self._fwd_stage_off += self._stage_len[bn]
-                            self._irb_stage[bn] = off
-                            P.k(L.irb_cov_reduce, self.irb_cov_rows.data_ptr(), crow.value, op.cin, self.sync_stage[off:].data_ptr())
-                        else:
-                            P.k(L.irb_cov_reduce, self.irb_cov_rows.data_ptr(), crow.value, op.cin, self.irb_cov_sums.data_ptr())
-                    if self._irb_keep_z:
-                        P.k(L.pwconv_fwd_wt, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pt), None, self.tptr(op.out), op.out.ld, None,
-                            ctypes.byref(ctypes.c_int(0)), N * op.Ho * op.Wo, op.cin, op.cout)
-                elif op in self._irb_dw:
-                    rec = self._irb_dw[op]
-                    P.k(L.irb_fwd, *self._irb_args(rec), st.ptr(op.w), self.tptr(op.out), op.out.ld, part, ctypes.byref(rows),
-                        *self._irb_geo(rec), tag=op.name)
-                elif self.bf16:
-                    self._conv_forward_bf16(P, op, xp, ldx, sp, hp, act, part, rows)
-                elif k == 'conv_pw' and self._use_sb(op, True, part is not None):
-                    wsp, pitch = st.sb_ptr(op, True)
-                    P.k(L.pwconv_fwd_sb, xp, ldx, sp, hp, act, wsp, pitch, st.ptr(op.b) if op.b else None,
-                        self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N * op.Ho * op.Wo, op.cin, op.cout,
-                        tag='pw:' + op.name)
-                elif k == 'conv_pw' and self.splitk_ws is not None and L.pwconv_fwd_splitk_plan(N * op.Ho * op.Wo, op.cin, op.cout):
-                    # few rows, long reduction (Xception's / ResNet50's ASPP 1x1 convs on the 33 x 33 map): split-K, two launches
-                    P.k(L.pwconv_fwd_wt_splitk, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pt), st.ptr(op.b) if op.b else None,
-                        self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), self.splitk_ws.data_ptr(), self.splitk_ws.numel() * 4,
-                        N * op.Ho * op.Wo, op.cin, op.cout, tag='pw:' + op.name)
-                elif k == 'conv_pw':
-                    P.k(L.pwconv_fwd_wt, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pt), st.ptr(op.b) if op.b else None,
-                        self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N * op.Ho * op.Wo, op.cin, op.cout,
-                        tag='pw:' + op.name)
-                elif k == 'conv_dw':
-                    if self._up_args(op) is not None:
-                        P.k(L.dw_upsampled_input, *self._up_args(op))
-                    P.k(L.dwconv2d_fwd, xp, ldx, sp, hp, act, st.ptr(op.w), self.tptr(op.out), op.out.ld, part,
-                        ctypes.byref(rows), N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l,
-                        op.Ho, op.Wo, tag=op.name)
-                elif self._stem_direct(op):
-                    P.k(L.stem_conv_fwd, xp, ldx, st.ptr(op.w), self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N,
-                        xt.H, xt.W, op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo, tag=op.name)
-                elif self._narrow(op):
-                    P.k(L.conv_narrow_fwd, xp, ldx, sp, hp, act, st.ptr(op.w), self.tptr(op.out), op.out.ld, part,
-                        ctypes.byref(rows), N, xt.H, xt.W, op.cin, op.cout, tag=op.name)
-                elif self._dense_gemm(op) and self._use_sb_dense(op, 1 if part is not None else 0):
-                    wsp, pitch = st.sb_ptr(op, True)
-                    P.k(L.conv2d_gemm_fwd_sb, xp, ldx, sp, hp, act, wsp, pitch, st.ptr(op.b) if op.b else None,
-                        self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N, xt.H, xt.W, op.cin, op.cout, op.k,
-                        op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo, tag=op.name)
-                elif self._dense_gemm(op):
-                    P.k(L.conv2d_gemm_fwd, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pt), st.ptr(op.b) if op.b else None,
-                        self.tptr(op.out), op.out.ld, part, ctypes.byref(rows), N, xt.H, xt.W, op.cin, op.cout, op.k,
-                        op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo, tag=op.name)
-                else:
-                    # what is left (Cin not a multiple of 4, e.g. a 7x7 RGB stem): im2col once, then the MFMA GEMM
-                    P.k(L.im2col, xp, ldx, sp, hp, act, self.tptr(op.col), op.col.ld, N, xt.H, xt.W, op.cin, op.k,
-                        op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                    P.k(L.pwconv_fwd_wt, self.tptr(op.col), op.col.ld, None, None, ACT_NONE, st.ptr(op.w, st.Pt),
-                        st.ptr(op.b) if op.b else None, self.tptr(op.out), op.out.ld, part, ctypes.byref(rows),
-                        N * op.Ho * op.Wo, op.kp, op.cout)
-                op.rows = rows.value
+            if k in CONV_KINDS:
+                self._conv_forward(P, op)
             elif k == 'conv_deconv':
                 # Conv2DTranspose(filters, 2, strides=(2, 2)) + bias: one GEMM whose epilogue scatters the four quadrants (csrc/deconv.hip)
                 assert not self.bf16, 'dl3p_deconv2x2_* has no bf16 twin (model._NO_BF16_TRAINING refuses the U-Net types)'
-                xp, ldx, sp, hp, act = self.vargs(op.x)
-                xt = op.x.tensor
-                P.k(L.deconv2x2_fwd, xp, ldx, sp, hp, act, st.ptr(op.w), st.ptr(op.b) if op.b else None, self.tptr(op.out),
-                    op.out.ld, N, xt.H, xt.W, op.cin, op.cout, tag=op.name)
+                P.k(L.deconv2x2_fwd, *self.vargs(op.x), st.ptr(op.w), st.ptr(op.b) if op.b else None, self.tptr(op.out),
+                    op.out.ld, *self._geo(op, 'io'), tag=op.name)
             elif k == 'pad_channels':
                 # zero-padded copy (a 1 x 1 im2col whose rows are padded to the wider tensor); no gradient
                 xt, t = op.x.tensor, op.out
@@ -1036,39 +1072,34 @@ class Executor:
             elif k == 'bn':
                 self._bn_forward(P, op)
             elif k == 'materialize':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
                 rp = ldr = rsp = rhp = None
                 ract = ACT_NONE
                 if op.r is not None:
                     rp, ldr, rsp, rhp, ract = self.vargs(op.r)
                 rate = op.rate if train else 0.0
                 t = op.out
-                P.k(L.affine_act_bf16 if self.bf16 else L.affine_act, xp, ldx, sp, hp, act, rp, ldr or 0, rsp, rhp, ract, float(rate),
+                P.k(L.affine_act_bf16 if self.bf16 else L.affine_act, *self.vargs(op.x), rp, ldr or 0, rsp, rhp, ract, float(rate),
                     self._dropout_seed(op), self.step.data_ptr(), self.tptr(t), t.ld, N * t.H * t.W, t.C)
             elif k == 'gap':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
                 xt = op.x.tensor
-                P.k(L.global_avgpool_fwd_bf16 if self.bf16 else L.global_avgpool_fwd, xp, ldx, sp, hp, act, self.tptr(op.out),
+                P.k(L.global_avgpool_fwd_bf16 if self.bf16 else L.global_avgpool_fwd, *self.vargs(op.x), self.tptr(op.out),
                     op.out.ld, 1.0, N, xt.H * xt.W, xt.C, self.pool_ws.data_ptr(), self.pool_wsb)
             elif k == 'maxpool':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
                 xt, t = op.x.tensor, op.out
                 arg = None
                 if train:          # the backward pass reads the winning taps instead of re-evaluating the windows
                     arg = self._pool_arg[op] = torch.empty(N * op.Ho * op.Wo * xt.C, dtype=torch.uint8, device=self.dev)
-                P.k(L.maxpool2d_fwd_bf16 if self.bf16 else L.maxpool2d_fwd, xp, ldx, sp, hp, act, self.tptr(t), t.ld,
+                P.k(L.maxpool2d_fwd_bf16 if self.bf16 else L.maxpool2d_fwd, *self.vargs(op.x), self.tptr(t), t.ld,
                     None if arg is None else arg.data_ptr(), N,
                     xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
             elif k == 'avgpool':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
                 xt, t = op.x.tensor, op.out
-                P.k(L.avgpool2d_fwd_bf16 if self.bf16 else L.avgpool2d_fwd, xp, ldx, sp, hp, act, self.tptr(t), t.ld, N,
+                P.k(L.avgpool2d_fwd_bf16 if self.bf16 else L.avgpool2d_fwd, *self.vargs(op.x), self.tptr(t), t.ld, N,
                     xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
             elif k == 'se_mul':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
                 s_ptr, lds, _, _, sact = self.vargs(op.s)
                 t = op.out
-                P.k(L.scale_bcast_fwd_bf16 if self.bf16 else L.scale_bcast_fwd, xp, ldx, sp, hp, act, s_ptr, lds, sact,
+                P.k(L.scale_bcast_fwd_bf16 if self.bf16 else L.scale_bcast_fwd, *self.vargs(op.x), s_ptr, lds, sact,
                     self.tptr(t), t.ld, N, t.H * t.W, t.C)
             elif k in ('resize', 'broadcast'):
                 if op in self._up_resize:
@@ -1080,20 +1111,21 @@ class Executor:
                 raise NotImplementedError(k)
         if self._fwd_pending:
             self._flush_bn_forward(P)
-        # head: pred_resize + softmax (+ loss and its gradient when training)
         P.ctx = 'head'
+        self._head_forward(P)
+        return P
+
+    def _head_forward(self, P):
+        """pred_resize + softmax (+ loss and its gradient when training)"""
+        L, N, train = self.L, self.N, self.training
         zt = self.head.tensor
         rows = ctypes.c_int(0)
         if train and self.fused_head:
             # loss + d loss / d (conv_upsample output) in one launch; the full-resolution gradient is never written
-            if self.fused_head_rows:
-                P.k(L.head_train_rows, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
-                    1.0 / float(N * self.H * self.W), self.tptr(zt, True), zt.ld, 0, self.loss_partials.data_ptr(),
-                    ctypes.byref(rows), self.head_ws.data_ptr(), self.head_wsb, N, zt.H, zt.W, self.C, self.H, self.W)
-            else:
-                P.k(L.head_train, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
-                    1.0 / float(N * self.H * self.W), self.tptr(zt, True), zt.ld, 0, self.loss_partials.data_ptr(),
-                    ctypes.byref(rows), N, zt.H, zt.W, self.C, self.H, self.W)
+            ws = (self.head_ws.data_ptr(), self.head_wsb) if self.fused_head_rows else ()
+            P.k(L.head_train_rows if self.fused_head_rows else L.head_train, self.tptr(zt), zt.ld, self.labels.data_ptr(),
+                int(self.ignore_index or 0), 1.0 / float(N * self.H * self.W), self.tptr(zt, True), zt.ld, 0,
+                self.loss_partials.data_ptr(), ctypes.byref(rows), *ws, N, zt.H, zt.W, self.C, self.H, self.W)
             P.k(L.reduce_rows, self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0)
         elif train:
             P.k(L.upsample_softmax_loss, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
@@ -1110,34 +1142,115 @@ class Executor:
             P.k(L.fill, self.metric_counts.data_ptr(), 0.0, N * 3 * self.C)       # int32 zeros share the bit pattern
             P.k(L.class_counts, self.tptr(zt), zt.ld, self.labels.data_ptr(), self.metric_counts.data_ptr(), N, zt.H, zt.W,
                 self.C, self.H, self.W)
-        return P
 
-    def _conv_forward_bf16(self, P, op, xp, ldx, sp, hp, act, part, rows):
-        L, N, st, k = self.L, self.N, self.store, op.kind
-        xt = op.x.tensor
-        if k == 'conv_pw':
-            P.k(L.pwconv_fwd_bf16, xp, ldx, self._is_f32(xt), sp, hp, act, st.ptr(op.w, st.Pbt), st.ptr(op.b) if op.b else None,
-                self.tptr(op.out), op.out.ld, self._is_f32(op.out), part, ctypes.byref(rows), N * op.Ho * op.Wo, op.cin, op.cout)
-        elif k == 'conv_dw':
-            P.k(L.dwconv2d_fwd_bf16, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pb), self.tptr(op.out), op.out.ld, part,
-                ctypes.byref(rows), N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo,
-                tag=op.name)
+    def _conv_forward(self, P, op):
+        """one conv of the forward plan, on the kernel family of its route; op.rows: the partial rows of BatchNorm statistics it left"""
+        bn = op.bn
+        want_stats = self.training and bn is not None and bn.layer.trainable
+        part = self.partials.data_ptr() if want_stats else None
+        rows = ctypes.c_int(0)
+        r = self._route(op)
+        if r in (R_GHOST_PW, R_GHOST_DW, R_IRB_EXPAND, R_IRB_DW):
+            self._conv_forward_fused(P, op, r, part, rows)
+        elif self.bf16:
+            self._conv_forward_bf16(P, op, r, part, rows)
         else:
-            P.k(L.im2col_bf16, xp, ldx, sp, hp, act, self.tptr(op.col), op.col.ld, N, xt.H, xt.W, op.cin, op.k, op.stride,
-                op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-            P.k(L.pwconv_fwd_bf16, self.tptr(op.col), op.col.ld, 0, None, None, ACT_NONE, st.ptr(op.w, st.Pbt),
-                st.ptr(op.b) if op.b else None, self.tptr(op.out), op.out.ld, self._is_f32(op.out), part, ctypes.byref(rows),
-                N * op.Ho * op.Wo, op.kp, op.cout)
+            self._conv_forward_f32(P, op, r, part, rows)
+        op.rows = rows.value
+
+    def _conv_forward_fused(self, P, op, r, part, rows):
+        """the two convs of a fused ghost module (_find_ghost) or of a fused inverted-residual block (_find_irb)"""
+        L, N, st = self.L, self.N, self.store
+        xt = op.x.tensor
+        if r == R_GHOST_PW:
+            pass                    # (written by the fused launch at the module's depthwise op: _find_ghost)
+        elif r == R_GHOST_DW:
+            e, b, d = self._ghost_dw[op]
+            P.k(L.ghost_fwd, *self.vargs(e.x), st.ptr(e.w), *self._bn_coeffs(e.bn), e.bn.act, st.ptr(op.w), self.tptr(e.out),
+                e.out.ld, N, xt.H, xt.W, e.cin, e.cout, tag=op.name)
+        elif r == R_IRB_EXPAND:
+            # fused block: the expand output is never formed.  Its BatchNorm's statistics come from the covariance of the
+            # block INPUT (z = x W is linear): one pass over the K-channel tensor, finalised at the 'bn' op
+            x = self.vargs(op.x)
+            if part is not None:
+                crow = ctypes.c_int(0)
+                P.k(L.irb_cov_stats, *x, self.irb_cov_rows.data_ptr(), self.irb_cov_cap, ctypes.byref(crow), N * xt.H * xt.W, op.cin)
+                sums = self.irb_cov_sums
+                if self.sync_bn:
+                    off = self._fwd_stage_off
+                    self._fwd_stage_off += self._stage_len[op.bn]
+                    self._irb_stage[op.bn] = off
+                    sums = self.sync_stage[off:]
+                P.k(L.irb_cov_reduce, self.irb_cov_rows.data_ptr(), crow.value, op.cin, sums.data_ptr())
+            if self._irb_keep_z:
+                P.k(L.pwconv_fwd_wt, *x, st.ptr(op.w, st.Pt), None, self.tptr(op.out), op.out.ld, None,
+                    ctypes.byref(ctypes.c_int(0)), *self._mkn(op))
+        else:
+            # (the depthwise conv of a fused inverted-residual block reads no buffer of its own: its input is recomputed)
+            rec = self._irb_dw[op]
+            P.k(L.irb_fwd, *self._irb_args(rec), st.ptr(op.w), self.tptr(op.out), op.out.ld, part, ctypes.byref(rows),
+                *self._irb_geo(rec), tag=op.name)
+
+    def _conv_forward_f32(self, P, op, r, part, rows):
+        L, st = self.L, self.store
+        x = self.vargs(op.x)
+        b = getattr(op, 'b', None)
+        bias = st.ptr(b) if b else None
+        out = (self.tptr(op.out), op.out.ld, part, ctypes.byref(rows))
+        if r == R_PW and self._use_sb(op, True, part is not None):
+            P.k(L.pwconv_fwd_sb, *x, *st.sb_ptr(op, True), bias, *out, *self._mkn(op), tag='pw:' + op.name)
+        elif r == R_PW and self.splitk_ws is not None and L.pwconv_fwd_splitk_plan(*self._mkn(op)):
+            # few rows, long reduction (Xception's / ResNet50's ASPP 1x1 convs on the 33 x 33 map): split-K, two launches
+            P.k(L.pwconv_fwd_wt_splitk, *x, st.ptr(op.w, st.Pt), bias, *out, self.splitk_ws.data_ptr(), self.splitk_ws.numel() * 4,
+                *self._mkn(op), tag='pw:' + op.name)
+        elif r == R_PW:
+            P.k(L.pwconv_fwd_wt, *x, st.ptr(op.w, st.Pt), bias, *out, *self._mkn(op), tag='pw:' + op.name)
+        elif r == R_DW:
+            if self._up_args(op) is not None:
+                P.k(L.dw_upsampled_input, *self._up_args(op))
+            P.k(L.dwconv2d_fwd, *x, st.ptr(op.w), *out, *self._geo(op, 'dw'), tag=op.name)
+        elif r == R_STEM:
+            P.k(L.stem_conv_fwd, x[0], x[1], st.ptr(op.w), *out, *self._geo(op, 'stem'), tag=op.name)
+        elif r == R_NARROW:
+            P.k(L.conv_narrow_fwd, *x, st.ptr(op.w), *out, *self._geo(op, 'io'), tag=op.name)
+        elif r == R_GEMM and self._use_sb_dense(op, 1 if part is not None else 0):
+            P.k(L.conv2d_gemm_fwd_sb, *x, *st.sb_ptr(op, True), bias, *out, *self._geo(op, 'dense'), tag=op.name)
+        elif r == R_GEMM:
+            P.k(L.conv2d_gemm_fwd, *x, st.ptr(op.w, st.Pt), bias, *out, *self._geo(op, 'dense'), tag=op.name)
+        else:
+            # what is left (Cin not a multiple of 4, e.g. a 7x7 RGB stem): im2col once, then the MFMA GEMM
+            P.k(L.im2col, *x, self.tptr(op.col), op.col.ld, *self._geo(op, 'dw'))
+            P.k(L.pwconv_fwd_wt, self.tptr(op.col), op.col.ld, None, None, ACT_NONE, st.ptr(op.w, st.Pt), bias, *out,
+                *self._mkn(op))
+
+    def _conv_forward_bf16(self, P, op, r, part, rows):
+        L, st = self.L, self.store
+        xp, ldx, sp, hp, act = self.vargs(op.x)
+        b = getattr(op, 'b', None)
+        bias = st.ptr(b) if b else None
+        if r == R_PW:
+            P.k(L.pwconv_fwd_bf16, xp, ldx, self._is_f32(op.x.tensor), sp, hp, act, st.ptr(op.w, st.Pbt), bias,
+                self.tptr(op.out), op.out.ld, self._is_f32(op.out), part, ctypes.byref(rows), *self._mkn(op))
+        elif r == R_DW:
+            P.k(L.dwconv2d_fwd_bf16, xp, ldx, sp, hp, act, st.ptr(op.w, st.Pb), self.tptr(op.out), op.out.ld, part,
+                ctypes.byref(rows), *self._geo(op, 'dw'), tag=op.name)
+        else:
+            P.k(L.im2col_bf16, xp, ldx, sp, hp, act, self.tptr(op.col), op.col.ld, *self._geo(op, 'dw'))
+            P.k(L.pwconv_fwd_bf16, self.tptr(op.col), op.col.ld, 0, None, None, ACT_NONE, st.ptr(op.w, st.Pbt), bias,
+                self.tptr(op.out), op.out.ld, self._is_f32(op.out), part, ctypes.byref(rows), *self._mkn(op))
 
     def _dropout_seed(self, op):
         return (self.seed * 1000003 + zlib.crc32((op.dropout_name or '').encode()) % 65521) & 0x7FFFFFFFFFFFFFFF
 
+    def _bn_finalize_args(self, bn, count):
+        """the arguments dl3p_bn_finalize and dl3p_irb_bn_finalize_cov share, from the element count on"""
+        st, aux = self.store, self.bn_aux[bn]
+        lp = {p.key: p for p in bn.layer.params}
+        return (count, st.ptr(lp['gamma']), st.ptr(lp['beta']), bn.eps, bn.momentum, st.ptr(lp['moving_mean']),
+                st.ptr(lp['moving_variance']), self.moving_mode, *self._bn_coeffs(bn), aux['mean'].data_ptr(), aux['invstd'].data_ptr())
+
     def _bn_forward(self, P, op):
         bn, L, st, N = op.bn, self.L, self.store, self.N
-        aux = self.bn_aux[bn]
-        lp = {p.key: p for p in bn.layer.params}
-        sp = self.gscale[bn.group.id].data_ptr() + 4 * bn.offset
-        hp = self.gshift[bn.group.id].data_ptr() + 4 * bn.offset
         z = op.z
         count = float(N * z.H * z.W)
         if self.training and bn.layer.trainable and self.sync_bn and op in self._irb_bn:
@@ -1152,18 +1265,14 @@ class Executor:
             self._fwd_pending.append((op, off, P.ctx))
         elif self.training and bn.layer.trainable and op in self._irb_bn:
             e = self._irb_bn[op][0]
-            P.k(L.irb_bn_finalize_cov, self.irb_cov_sums.data_ptr(), st.ptr(e.w), e.cin, e.cout, count, st.ptr(lp['gamma']),
-                st.ptr(lp['beta']), bn.eps, bn.momentum, st.ptr(lp['moving_mean']), st.ptr(lp['moving_variance']),
-                self.moving_mode, sp, hp, aux['mean'].data_ptr(), aux['invstd'].data_ptr())
+            P.k(L.irb_bn_finalize_cov, self.irb_cov_sums.data_ptr(), st.ptr(e.w), e.cin, e.cout, *self._bn_finalize_args(bn, count))
         elif self.training and bn.layer.trainable:
-            rows = op.producer.rows
-            sums = None
-            P.k(L.bn_finalize, self.partials.data_ptr(), rows, sums, bn.C, count, st.ptr(lp['gamma']),
-                st.ptr(lp['beta']), bn.eps, bn.momentum, st.ptr(lp['moving_mean']), st.ptr(lp['moving_variance']),
-                self.moving_mode, sp, hp, aux['mean'].data_ptr(), aux['invstd'].data_ptr())
+            P.k(L.bn_finalize, self.partials.data_ptr(), op.producer.rows, None, bn.C, *self._bn_finalize_args(bn, count))
         else:
+            aux = self.bn_aux[bn]
+            lp = {p.key: p for p in bn.layer.params}
             P.k(L.bn_infer_coeffs, st.ptr(lp['gamma']), st.ptr(lp['beta']), st.ptr(lp['moving_mean']),
-                st.ptr(lp['moving_variance']), bn.eps, sp, hp, aux['mean'].data_ptr(), aux['invstd'].data_ptr(), bn.C)
+                st.ptr(lp['moving_variance']), bn.eps, *self._bn_coeffs(bn), aux['mean'].data_ptr(), aux['invstd'].data_ptr(), bn.C)
 
     def _reads_pending(self, op):
         """does `op` apply the coefficients of a BatchNorm whose statistics are still waiting for their all-reduce?"""
@@ -1189,36 +1298,27 @@ class Executor:
         pend, self._fwd_pending = self._fwd_pending, []
         lo = pend[0][1]
         hi = pend[-1][1] + self._stage_len[pend[-1][0].bn]
-        ctx = P.ctx
-        P.ctx = 'syncbn:' + '+'.join(b.bn.name for b, _, _ in pend)
-        P.coll(lambda t=self.sync_stage[lo:hi]: self.dist.all_reduce(t))
+        with P.at('syncbn:' + '+'.join(b.bn.name for b, _, _ in pend)):
+            P.coll(lambda t=self.sync_stage[lo:hi]: self.dist.all_reduce(t))
         st, L = self.store, self.L
         for op, off, c in pend:
             bn = op.bn
-            P.ctx = c
-            aux = self.bn_aux[bn]
-            lp = {p.key: p for p in bn.layer.params}
-            sp = self.gscale[bn.group.id].data_ptr() + 4 * bn.offset
-            hp = self.gshift[bn.group.id].data_ptr() + 4 * bn.offset
-            count = float(self.N * op.z.H * op.z.W) * self.dist.world_size
-            if op in self._irb_bn:
-                e = self._irb_bn[op][0]
-                P.k(L.irb_bn_finalize_cov, self.sync_stage[off:].data_ptr(), st.ptr(e.w), e.cin, e.cout, count, st.ptr(lp['gamma']),
-                    st.ptr(lp['beta']), bn.eps, bn.momentum, st.ptr(lp['moving_mean']), st.ptr(lp['moving_variance']),
-                    self.moving_mode, sp, hp, aux['mean'].data_ptr(), aux['invstd'].data_ptr())
-                continue
-            P.k(L.bn_finalize, None, 0, self.sync_stage[off:].data_ptr(), bn.C, count, st.ptr(lp['gamma']),
-                st.ptr(lp['beta']), bn.eps, bn.momentum, st.ptr(lp['moving_mean']), st.ptr(lp['moving_variance']),
-                self.moving_mode, sp, hp, aux['mean'].data_ptr(), aux['invstd'].data_ptr())
-        P.ctx = ctx
+            tail = self._bn_finalize_args(bn, float(self.N * op.z.H * op.z.W) * self.dist.world_size)
+            with P.at(c):
+                if op in self._irb_bn:
+                    e = self._irb_bn[op][0]
+                    P.k(L.irb_bn_finalize_cov, self.sync_stage[off:].data_ptr(), st.ptr(e.w), e.cin, e.cout, *tail)
+                else:
+                    P.k(L.bn_finalize, None, 0, self.sync_stage[off:].data_ptr(), bn.C, *tail)
 
     # ---------------------------------------------------------------- backward
     def _acc(self, t):
         """accumulate flag for a write into grad(t): 0 the first time, 1 afterwards"""
+        written = self._bt.written
         key = t.id
-        if key in self._written or (t.base is not None and t.base.id in self._written):
+        if key in written or (t.base is not None and t.base.id in written):
             return 1
-        self._written.add(key)
+        written.add(key)
         return 0
 
     def _gbuf(self, v):
@@ -1229,7 +1329,7 @@ class Executor:
             # gradient (g * act'(T)) when backward reaches T's producer.  (view_parts: a BatchNorm-free Concatenate, one view
             # buffer over all branches -- each branch's slice is folded at that branch's producer; graph.concat_act)
             for tt, act, pv in getattr(v, 'view_parts', None) or [(v.tensor, v.act, vt)]:
-                self._pending_views.setdefault(tt.id, []).append((tt, act, pv))
+                self._bt.pending_views.setdefault(tt.id, []).append((tt, act, pv))
             return self.tptr(vt, grad=True), vt.ld, vt
         # a Concatenate value carries the activation of its branches: each branch's BatchNormalization
         # backward applies act' to its own channel slice, so the buffer itself takes the plain gradient
@@ -1237,10 +1337,15 @@ class Executor:
             raise NotImplementedError('activation-only lazy value without a view buffer: ' + v.tensor.name)
         return self.tptr(v.tensor, grad=True), v.tensor.ld, v.tensor
 
+    def _gbuf_acc(self, v):
+        """(ptr, ld, accumulate flag): where a data gradient writes d/d(value v)"""
+        gp, ldg, keyt = self._gbuf(v)
+        return gp, ldg, self._acc(keyt)
+
     def _flush_views(self, P, t):
         """T.grad (+)= view.grad * act'(T) for every bare-activation view of T"""
         done = set()
-        for (tt, act, vt) in self._pending_views.pop(t.id, []):
+        for (tt, act, vt) in self._bt.pending_views.pop(t.id, []):
             if vt.id in done:
                 continue
             done.add(vt.id)
@@ -1248,10 +1353,9 @@ class Executor:
                 tt.ld, None, None, act, None, None, None, self.tptr(tt, True), tt.ld, self._acc(tt), self.N * tt.H * tt.W, tt.C)
 
     def _trace_backward(self):
-        P, L, N, st = Plan(), self.L, self.N, self.store
-        self._written = set()
-        self._pending_views = {}
-        G = st.G
+        P, L, N = Plan(), self.L, self.N
+        T = self._bt = BackwardTrace()
+        G = self.store.G
         zt = self.head.tensor
         # d(loss)/d(pred_resize output) -> d/d(conv_upsample output): transpose of the bilinear upsample
         if zt.requires_grad and self.fused_head:
@@ -1259,392 +1363,38 @@ class Executor:
         elif zt.requires_grad:
             P.k(L.resize_bilinear_bwd, self.dlogits_big.data_ptr(), self.cpad, self.tptr(zt, True), zt.ld,
                 self._acc(zt), N, zt.H, zt.W, zt.C, self.H, self.W)
-        ws, wsb = self.workspace.data_ptr(), self.workspace.numel() * 4
-        # data parallel: the flat gradient buffer is produced back to front; each finished bucket is
-        # all-reduced on the side stream while the remaining backward kernels run
-        bucket_edges = self._bucket_edges() if self.dist is not None else {}
-        # SyncBatchNorm: a layer's weight gradient feeds nothing in the backward chain, so it is held back and
-        # issued while the NEXT BatchNorm's statistics all-reduce is on the wire (hides the collective's latency)
-        self._deferred = []
-        defer = self.sync_bn
-        self._deferred_mode = bool(defer)
-        fuse = self._bn_fusion_map()
-        if self.bf16:
-            # bf16: the pointwise GEMMs can carry the sums (dl3p_pwconv_bwd_data_bn_bf16, more than 64 rows), the depthwise
-            # kernels cannot.  Opt-in: measured slower than the separate reduce pass (the epilogue meets z in 8-byte pieces:
-            # MobileNetV2 513x513 batch 16 12.37 against 11.83 ms, MobileNetV3-Large 1024x2048 batch 1 6.92 against 6.86)
-            fuse = {c: b for c, b in fuse.items() if c.kind == 'conv_pw' and self.N * c.Ho * c.Wo > 64
-                    and os.environ.get('DL3P_BF16_FUSE_BN_BWD', '0') == '1'}
-        bn_done = set()
-        self._bwd_pending, self._bwd_stage_off = [], self._sync_total
-        processed = set()
-        readers = self._bn_readers()
-        bn_of = {id(o.z): o for o in self.g.ops if o.kind == 'bn'}
-        self._galias = {}                 # z tensor id -> (ptr, ld) of the buffer that already holds d/d(BN(z) output)
-        alias_ok = os.environ.get('DL3P_GRAD_ALIAS', '1') != '0'
-        self._sync_g = {}                 # SyncBatchNorm: 'bn' op -> (ptr, ld) its apply reads the gradient from (after the all-reduce)
-        # BatchNorm -> residual Add -> pointwise conv: the conv's data gradient is the last writer of d/d(Add output), which
-        # IS the gradient of the BatchNorm output, so it carries that BatchNorm's backward sums too (no bn_bwd_reduce pass)
-        fuse_add = self._bn_fusion_through_adds(readers) if not self.bf16 else {}
-        self._presums = {}                # 'bn' op -> partial rows left in self.partials2 by such a data gradient
+        bucket_edges = self._begin_backward(T)
         rops = list(reversed(self.g.ops))
-        self._bwd_ctx = (fuse, fuse_add, bn_done)       # (what a fused block's second pass needs when it is issued from a flush)
-
-        def wgrad(fn, *args):
-            if defer:
-                self._deferred.append((fn, args, P.ctx))
-            else:
-                P.k(fn, *args)
-
-        # the weight-gradient kernels leave their (fp32) slabs in per-layer regions of one buffer and ONE pair of launches
-        # reduces them all (dl3p_reduce_rows_batched; 65 reduce launches of 5-13 us each otherwise) -- at the end of
-        # backward on one GPU, per gradient bucket under data parallelism (in front of the bucket's all-reduce).  Same
-        # per-element arithmetic as the per-layer reduction, whichever way the jobs are grouped.
-        batch = os.environ.get('DL3P_BATCHED_WGRAD', '1') != '0'
-        self._batch_wgrad = batch and not defer
-        if self._batch_wgrad and not self.bf16 and getattr(self, 'dz_scratch', None) is None:
-            need = max([N * op.Ho * op.Wo * (op.cout if op.kind == 'conv_pw' else op.c) for op in self.g.ops
-                        if op.kind in ('conv_pw', 'conv_dw') and op not in self._irb_expand] or [0])
-            self.dz_scratch = torch.zeros(need + 64, **self.f32)      # dz of the layer whose weight gradient just ran
-        self._folded = {}                 # z tensor id -> BatchNorm-backward apply arguments taken over by the conv's wgrad
-        self._dz_not_kept = set()         # (debug record) z tensors whose gradient buffer still holds d/d(BN output) after backward
-        self._folded_dg = {}              # ... taken over by the conv's DATA gradient (row-stationary split GEMM, pw_split_rs.hip)
-        jobs = self._jobs = []            # (slab pointer, destination pointer, rows, n) issued and not yet reduced
-        self._wgrad_tables = []
-        slab_off = self._slab_off = [0]
-        slab_need = 0
-        if batch:
-            for op in self.g.ops:
-                if op.kind in ('conv_pw', 'conv_dense', 'conv_dw') and op.layer.trainable and self._slab_bytes(op):
-                    slab_need += (self._slab_bytes(op) + 255) // 256 * 256
-            self.slab_ws = torch.zeros(slab_need // 4 + 64, **self.f32) if slab_need else None
-
-        def wgrad_slabs(fn, n, dst, nbytes, *args, up=None):
-            """fn(*args[:split], region, bytes, &rows, *args[split:]) with args given as (before, after); up: the arguments of the
-            dl3p_dw_upsampled_input call that describes this launch's input (a conv that absorbed its resize)"""
-            before, after = args
-            region = self.slab_ws.data_ptr() + 4 * slab_off[0]
-            slab_off[0] += ((nbytes + 255) // 256 * 256) // 4
-
-            def issue(P2):
-                rows = ctypes.c_int(0)
-                if up is not None:
-                    P2.k(L.dw_upsampled_input, *up)
-                P2.k(fn, *before, region, nbytes, ctypes.byref(rows), *after)
-                self._jobs.append((region, dst, rows.value, n))
-            if defer:
-                self._deferred.append((issue, None, P.ctx))      # runs at the next _flush_deferred, like the plain ones
-            else:
-                issue(P)
         for ri, op in enumerate(rops):
-            k = op.kind
             P.ctx = _op_label(op)
+            out = getattr(op, 'out', None)
             # SyncBatchNorm: the producer of a pending BatchNorm's input needs that BatchNorm's dz now
-            if self._bwd_pending and getattr(op, 'out', None) is not None and any(b.z is op.out for b, _, _ in self._bwd_pending):
+            if T.pending and out is not None and any(b.z is out for b, _, _ in T.pending):
                 self._flush_bn_backward(P)
             if op in bucket_edges:
                 self._flush_deferred(P)        # every gradient of the finished bucket must have been produced
                 self._reduce_pending(P)        # ... and reduced from its slabs
                 lo, hi = bucket_edges[op]
                 P.coll(lambda lo=lo, hi=hi: self.dist.all_reduce_async(G[lo:hi]))
-            out = getattr(op, 'out', None)
-            if out is not None and out.id in self._pending_views:
+            if out is not None and out.id in T.pending_views:
                 self._flush_views(P, out)
-            if k == 'bn':
-                if op.z.requires_grad and op not in bn_done:
-                    self._bn_backward(P, op)
-                    bn_done.add(op)
-                    if self.sync_bn and op.bn.layer.trainable:
-                        # other BatchNorms whose gradient is complete already (every reader of their output has been
-                        # processed: the ASPP branches behind concat_projection, a shortcut beside its residual branch):
-                        # take their local sums now, so that one all-reduce serves them all
-                        for op2 in rops[ri + 1:]:
-                            if (op2.kind == 'bn' and op2 not in bn_done and op2.z.requires_grad and op2.bn.layer.trainable
-                                    and readers.get(op2) and readers[op2] <= processed and op2 not in fuse.values()):
-                                ctx = P.ctx
-                                P.ctx = _op_label(op2)
-                                self._bn_backward(P, op2)
-                                bn_done.add(op2)
-                                P.ctx = ctx
-                processed.add(op)
-                continue
-            processed.add(op)
-            if out is None or not out.requires_grad:
+            if op.kind == 'bn':
+                self._backward_bn(P, op, rops[ri + 1:])
+            T.processed.add(op)
+            if op.kind == 'bn' or out is None or not out.requires_grad:
                 continue
             if op in self._irb_expand:
-                continue                      # its gradients were produced together with the depthwise conv's (below)
+                continue                      # its gradients were produced together with the depthwise conv's
             if op in self._irb_dw:
-                self._irb_backward(P, self._irb_dw[op], fuse, fuse_add, bn_done, batch)
-                continue
-            if self.bf16 and k in ('conv_pw', 'conv_dense', 'conv_dw'):
-                fused_bn = fuse.get(op) if (op in fuse and fuse[op].z.requires_grad) else None
-                self._conv_backward_bf16(P, op, wgrad, ws, wsb, wgrad_slabs if batch else None, fused_bn)
-                if fused_bn is not None:
-                    bn_done.add(fused_bn)
-            elif k in ('conv_pw', 'conv_dense', 'conv_dw'):
-                xp, ldx, sp, hp, act = self.vargs(op.x)
-                xt = op.x.tensor
-                dz, lddz = self.tptr(out, True), out.ld
-                need_gx = xt.requires_grad or xt.root.requires_grad
-                dgrad_done = False
-                if k == 'conv_pw' and out.id in self._folded_dg:
-                    # data gradient FIRST: it forms dz = BatchNorm-backward apply of (g, z) in its staging pass and leaves it at
-                    # (dz, lddz) for the weight gradient below
-                    fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef, dz, lddz = self._folded_dg.pop(out.id)
-                    gp, ldg, keyt = self._gbuf(op.x)
-                    acc = self._acc(keyt)
-                    wsp, pitch = st.sb_ptr(op, False)
-                    M_ = N * op.Ho * op.Wo
-                    fold_args = (fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef, dz, lddz, wsp, pitch, gp, ldg, acc, M_, op.cin, op.cout)
-                    front = fuse.get(op) if (op in fuse and fuse[op].z.requires_grad) else None
-                    front_add = fuse_add.get(op) if (front is None and op in fuse_add and fuse_add[op].z.requires_grad) else None
-                    bn_front = front or front_add
-                    rows_f = ctypes.c_int(0)
-                    if bn_front is not None:
-                        bnf = bn_front.bn
-                        auxf = self.bn_aux[bnf]
-                        part_f = self.partials if front is not None else self.partials2
-                        P.k(L.pwconv_bwd_data_sb_apply, *fold_args, self.tptr(bn_front.z), bn_front.z.ld,
-                            self.gscale[bnf.group.id].data_ptr() + 4 * bnf.offset, self.gshift[bnf.group.id].data_ptr() + 4 * bnf.offset,
-                            bnf.act, auxf['mean'].data_ptr(), auxf['invstd'].data_ptr(), part_f.data_ptr(), ctypes.byref(rows_f))
-                    else:
-                        P.k(L.pwconv_bwd_data_sb_apply, *fold_args, None, 0, None, None, ACT_NONE, None, None, None, None)
-                    dgrad_done = True
-                if op.layer.trainable and batch and self._slab_bytes(op):
-                    gw = st.ptr(op.w, G)
-                    nb = self._slab_bytes(op)
-                    if k == 'conv_pw' and out.id in self._folded:
-                        fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef = self._folded.pop(out.id)
-                        dz, lddz = (self.dz_scratch.data_ptr(), op.cout) if need_gx else (None, 0)
-                        wgrad_slabs(L.pwconv_bwd_weight_slabs_bn, op.cin * op.cout, gw, nb,
-                                    (xp, ldx, sp, hp, act, fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef, dz, lddz),
-                                    (N * op.Ho * op.Wo, op.cin, op.cout))
-                    elif k == 'conv_pw':
-                        wgrad_slabs(L.pwconv_bwd_weight_slabs, op.cin * op.cout, gw, nb, (xp, ldx, sp, hp, act, dz, lddz),
-                                    (N * op.Ho * op.Wo, op.cin, op.cout))
-                    elif k == 'conv_dw' and out.id in self._folded:
-                        fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef = self._folded.pop(out.id)
-                        dz, lddz = (self.dz_scratch.data_ptr(), op.c) if need_gx else (None, 0)
-                        wgrad_slabs(L.dwconv2d_bwd_weight_slabs_bn, op.k * op.k * op.c, gw, nb,
-                                    (xp, ldx, sp, hp, act, fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef, dz, lddz),
-                                    (N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo),
-                                    up=self._up_args(op))
-                    elif k == 'conv_dw':
-                        wgrad_slabs(L.dwconv2d_bwd_weight_slabs, op.k * op.k * op.c, gw, nb, (xp, ldx, sp, hp, act, dz, lddz),
-                                    (N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo),
-                                    up=self._up_args(op))
-                    elif self._stem_direct(op) and out.id in self._folded:
-                        # the stem has no data gradient: dz = BatchNorm-backward apply of (g, z) is formed in the weight gradient's
-                        # staging pass and never written
-                        fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef = self._folded.pop(out.id)
-                        wgrad_slabs(L.stem_conv_bwd_weight_slabs_bn, 28 * op.cout, gw, nb,
-                                    (xp, ldx, fg, fldg, fz, fldz, fsp, fhp, fact, fmean, finv, fcoef),
-                                    (N, xt.H, xt.W, op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo))
-                    elif self._stem_direct(op):
-                        wgrad_slabs(L.stem_conv_bwd_weight_slabs, 28 * op.cout, gw, nb, (xp, ldx, dz, lddz),
-                                    (N, xt.H, xt.W, op.cout, op.pad_t, op.pad_l, op.Ho, op.Wo))
-                    elif self._narrow(op):
-                        wgrad_slabs(L.conv_narrow_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, gw, nb,
-                                    (xp, ldx, sp, hp, act, dz, lddz), (N, xt.H, xt.W, op.cin, op.cout))
-                    else:
-                        wgrad_slabs(L.conv2d_gemm_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, gw, nb,
-                                    (xp, ldx, sp, hp, act, dz, lddz),
-                                    (N, xt.H, xt.W, op.cin, op.cout, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo))
-                elif op.layer.trainable:
-                    gw = st.ptr(op.w, G)
-                    if k == 'conv_pw':
-                        wgrad(L.pwconv_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, st.ptr(op.b, G) if op.b else None,
-                              ws, wsb, N * op.Ho * op.Wo, op.cin, op.cout)
-                    elif k == 'conv_dw':
-                        if self._up_args(op) is not None:
-                            wgrad(L.dw_upsampled_input, *self._up_args(op))
-                        wgrad(L.dwconv2d_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.c,
-                              op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                    elif self._stem_direct(op):
-                        wgrad(L.stem_conv_bwd_weight, xp, ldx, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.cout, op.pad_t,
-                              op.pad_l, op.Ho, op.Wo)
-                    elif self._narrow(op):
-                        wgrad(L.conv_narrow_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.cin,
-                              op.cout)
-                    elif self._dense_gemm(op):
-                        wgrad(L.conv2d_gemm_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, gw, st.ptr(op.b, G) if op.b else None,
-                              ws, wsb, N, xt.H, xt.W, op.cin, op.cout, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho,
-                              op.Wo)
-                    else:
-                        wgrad(L.pwconv_bwd_weight, self.tptr(op.col), op.col.ld, None, None, ACT_NONE, dz, lddz, gw,
-                              st.ptr(op.b, G) if op.b else None, ws, wsb, N * op.Ho * op.Wo, op.kp, op.cout)
-                if dgrad_done:
-                    # (the data gradient ran in front of the weight gradient; what is left is the BatchNorm in front of the conv)
-                    if front is not None:
-                        ctx = P.ctx
-                        P.ctx = _op_label(front)
-                        self._bn_backward(P, front, fused_rows=rows_f.value)
-                        P.ctx = ctx
-                        bn_done.add(front)
-                    elif front_add is not None:
-                        self._presums[front_add] = rows_f.value
-                elif need_gx:
-                    gp, ldg, keyt = self._gbuf(op.x)
-                    acc = self._acc(keyt)
-                    if k == 'conv_pw' and op in fuse and fuse[op].z.requires_grad:
-                        bn_op = fuse[op]
-                        bn = bn_op.bn
-                        aux = self.bn_aux[bn]
-                        rows = ctypes.c_int(0)
-                        self._pw_dgrad_bn(P, op, dz, lddz, gp, ldg, acc, bn_op, self.partials, rows)
-                        ctx = P.ctx
-                        P.ctx = _op_label(bn_op)
-                        self._bn_backward(P, bn_op, fused_rows=rows.value)
-                        P.ctx = ctx
-                        bn_done.add(bn_op)
-                    elif k == 'conv_pw' and op in fuse_add and fuse_add[op].z.requires_grad:
-                        bn_op = fuse_add[op]
-                        bn = bn_op.bn
-                        aux = self.bn_aux[bn]
-                        rows = ctypes.c_int(0)
-                        self._pw_dgrad_bn(P, op, dz, lddz, gp, ldg, acc, bn_op, self.partials2, rows)
-                        self._presums[bn_op] = rows.value
-                    elif k == 'conv_pw' and self._use_sb(op, False, False):
-                        wsp, pitch = st.sb_ptr(op, False)
-                        P.k(L.pwconv_bwd_data_sb, dz, lddz, wsp, pitch, gp, ldg, acc, N * op.Ho * op.Wo, op.cin, op.cout,
-                            None, 0, None, None, ACT_NONE, None, None, None, None)
-                    elif k == 'conv_pw':
-                        P.k(L.pwconv_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, acc, N * op.Ho * op.Wo, op.cin,
-                            op.cout)
-                    elif k == 'conv_dw' and op in fuse and fuse[op].z.requires_grad:
-                        bn_op = fuse[op]
-                        bn = bn_op.bn
-                        aux = self.bn_aux[bn]
-                        rows = ctypes.c_int(0)
-                        P.k(L.dwconv2d_bwd_data_bn, dz, lddz, st.ptr(op.w), gp, ldg, acc, N, xt.H, xt.W, op.c, op.k,
-                            op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo, self.tptr(bn_op.z), bn_op.z.ld,
-                            self.gscale[bn.group.id].data_ptr() + 4 * bn.offset,
-                            self.gshift[bn.group.id].data_ptr() + 4 * bn.offset, bn.act, aux['mean'].data_ptr(),
-                            aux['invstd'].data_ptr(), self.partials.data_ptr(), ctypes.byref(rows))
-                        ctx = P.ctx
-                        P.ctx = _op_label(bn_op)
-                        self._bn_backward(P, bn_op, fused_rows=rows.value)
-                        P.ctx = ctx
-                        bn_done.add(bn_op)
-                    elif k == 'conv_dw':
-                        P.k(L.dwconv2d_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, acc, N, xt.H, xt.W, op.c, op.k,
-                            op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                    elif k == 'conv_dense' and self._narrow(op):
-                        P.k(L.conv_narrow_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, acc, N, xt.H, xt.W, op.cin, op.cout)
-                    elif k == 'conv_dense' and self._dense_gemm(op) and op.k > 1:
-                        wd = self.dense_wd[id(op)]
-                        P.k(L.conv2d_gemm_dgrad_weights, st.ptr(op.w), wd.data_ptr(), op.k, op.cin, op.cout)
-                        if self._use_sb_dense(op, 2):
-                            # the re-laid kernel [Cin][k k Cout] split into its three bf16 planes (a few hundred KB), then the
-                            # data gradient on the bf16 matrix pipe
-                            kd = op.k * op.k * op.cout
-                            pitch = (kd + 31) // 32 * 32
-                            sp3 = self.dense_wd_sb.get(id(op))
-                            if sp3 is None:
-                                sp3 = self.dense_wd_sb[id(op)] = (torch.zeros(3 * op.cin * pitch, dtype=torch.int16, device=self.dev),
-                                                                  torch.tensor([[0, op.cin, kd, kd, 0, pitch]], dtype=torch.int64, device=self.dev))
-                            P.k(L.split_bf16x3_batch, wd.data_ptr(), sp3[0].data_ptr(), sp3[1].data_ptr(), 1)
-                            P.k(L.conv2d_gemm_bwd_data_sb, dz, lddz, sp3[0].data_ptr(), pitch, gp, ldg, acc, N, xt.H, xt.W, op.cin, op.cout,
-                                op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                        else:
-                            P.k(L.conv2d_gemm_bwd_data, dz, lddz, wd.data_ptr(), gp, ldg, acc, N, xt.H, xt.W, op.cin, op.cout,
-                                op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                    else:
-                        # d/d(im2col matrix) by the GEMM, then the transposed gather back onto the input pixels
-                        P.k(L.pwconv_bwd_data, dz, lddz, st.ptr(op.w), self.tptr(op.col, True), op.col.ld, 0,
-                            N * op.Ho * op.Wo, op.kp, op.cout)
-                        P.k(L.col2im, self.tptr(op.col, True), op.col.ld, gp, ldg, acc, N, xt.H, xt.W, op.cin, op.k,
-                            op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
-            elif k == 'conv_deconv':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
-                xt = op.x.tensor
-                dz, lddz = self.tptr(out, True), out.ld
-                if op.layer.trainable:
-                    wgrad(L.deconv2x2_bwd_weight, xp, ldx, sp, hp, act, dz, lddz, st.ptr(op.w, G), st.ptr(op.b, G) if op.b else None,
-                          ws, wsb, N, xt.H, xt.W, op.cin, op.cout)
-                if xt.requires_grad or xt.root.requires_grad:
-                    gp, ldg, keyt = self._gbuf(op.x)
-                    P.k(L.deconv2x2_bwd_data, dz, lddz, st.ptr(op.w), gp, ldg, self._acc(keyt), N, xt.H, xt.W, op.cin, op.cout)
-            elif k == 'materialize':
-                gt, ldt = self.tptr(out, True), out.ld
-                M = N * out.H * out.W
-                if op.x.tensor.requires_grad or op.x.tensor.root.requires_grad:
-                    xb = bn_of.get(id(op.x.tensor)) if op.x.bn is not None else None
-                    if (alias_ok and xb is not None and float(op.rate) == 0.0 and getattr(op.x, 'view_grad', None) is None
-                            and op.x.tensor.C == out.C and readers.get(xb) == {op} and op.x.tensor.id not in self._written
-                            and (op.x.tensor.base is None or op.x.tensor.base.id not in self._written)):
-                        # a residual Add hands its gradient to the BatchNorm branch unchanged: that BatchNorm's backward
-                        # reads it where it is (no copy into the branch's own buffer, one launch less per Add)
-                        self._galias[op.x.tensor.id] = (gt, ldt)
-                        self._written.add(op.x.tensor.id)
-                    else:
-                        gp, ldg, keyt = self._gbuf(op.x)
-                        P.k(L.scale_mask_bwd_bf16 if self.bf16 else L.scale_mask_bwd, gt, ldt, float(op.rate),
-                            self._dropout_seed(op), self.step.data_ptr(), gp, ldg, self._acc(keyt), M, out.C)
-                if op.r is not None and (op.r.tensor.requires_grad or op.r.tensor.root.requires_grad):
-                    rt = op.r.tensor
-                    rb = bn_of.get(id(rt)) if op.r.bn is not None else None
-                    fresh = (alias_ok and getattr(op.r, 'view_grad', None) is None and rt.C == out.C
-                             and rt.id not in self._written and (rt.base is None or rt.base.id not in self._written))
-                    if fresh and rb is not None and readers.get(rb) == {op}:
-                        self._galias[rt.id] = (gt, ldt)        # the other branch is a BatchNorm too (Xception shortcut)
-                        self._written.add(rt.id)
-                    elif (fresh and (op.r.is_plain or rb is not None) and rt.base is None and out.base is None and rt.ld == out.ld
-                          and rt.id in self.grad and out.id in self.grad
-                          and self.grad[rt.id].numel() == self.grad[out.id].numel()):
-                        # the identity branch: d/d(r) starts as d/d(out) and only ever gains contributions that are issued
-                        # after every reader of d/d(out) (the producer of r precedes this Add's other branch): the two
-                        # gradients share one buffer from here on, no copy
-                        self.grad[rt.id] = self.grad[out.id]
-                        self._written.add(rt.id)
-                    else:
-                        gp, ldg, keyt = self._gbuf(op.r)
-                        P.k(L.scale_mask_bwd_bf16 if self.bf16 else L.scale_mask_bwd, gt, ldt, 0.0, 0, None, gp, ldg,
-                            self._acc(keyt), M, out.C)
-            elif k == 'se_mul':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
-                s_ptr, lds, _, _, sact = self.vargs(op.s)
-                gp, ldg, keyx = self._gbuf(op.x)
-                gsp, ldgs, keys = self._gbuf(op.s)
-                assert self._acc(keys) == 0, 'SE scale gradient has a single producer'
-                P.k(L.scale_bcast_bwd_bf16 if self.bf16 else L.scale_bcast_bwd, self.tptr(out, True), out.ld, xp, ldx, sp, hp,
-                    act, s_ptr, lds, sact, gp, ldg,
-                    self._acc(keyx), gsp, ldgs, N, out.H * out.W, out.C, self.pool_ws.data_ptr(), self.pool_wsb)
-            elif k == 'maxpool':
-                xp, ldx, sp, hp, act = self.vargs(op.x)
-                xt = op.x.tensor
-                gp, ldg, keyt = self._gbuf(op.x)
-                if self.bf16:
-                    P.k(L.maxpool2d_bwd_bf16, self.tptr(out, True), out.ld, self._pool_arg[op].data_ptr(), gp, ldg, self._acc(keyt),
-                        N, xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
-                else:
-                    P.k(L.maxpool2d_bwd, xp, ldx, sp, hp, act, self.tptr(out, True), out.ld, self._pool_arg[op].data_ptr(), gp,
-                        ldg, self._acc(keyt), N, xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
-            elif k == 'avgpool':
-                # d/d(activated input); the producer's BatchNorm backward applies act' (as behind 'maxpool')
-                xt = op.x.tensor
-                gp, ldg, keyt = self._gbuf(op.x)
-                P.k(L.avgpool2d_bwd_bf16 if self.bf16 else L.avgpool2d_bwd, self.tptr(out, True), out.ld, gp, ldg, self._acc(keyt),
-                    N, xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
-            elif k == 'gap':
-                xt = op.x.tensor
-                gp, ldg, keyt = self._gbuf(op.x)
-                P.k(L.global_avgpool_bwd_bf16 if self.bf16 else L.global_avgpool_bwd, self.tptr(out, True), out.ld, gp, ldg,
-                    self._acc(keyt), N, xt.H * xt.W, xt.C)
-            elif k == 'broadcast':
-                # gradient w.r.t. the (lazy) 1x1 value = sum over the pixels it was broadcast to
-                xt = op.x.tensor
-                assert self._acc(xt) == 0
-                P.k(L.global_avgpool_fwd_bf16 if self.bf16 else L.global_avgpool_fwd, self.tptr(out, True), out.ld, None, None,
-                    ACT_NONE, self.tptr(xt, True), xt.ld, float(out.H * out.W), N, out.H * out.W, out.C,
-                    self.pool_ws.data_ptr(), self.pool_wsb)
-            elif k == 'resize':
-                xt = op.x.tensor
-                P.k(L.resize_bilinear_bwd_bf16 if self.bf16 else L.resize_bilinear_bwd, self.tptr(out, True), out.ld,
-                    self.tptr(xt, True), xt.ld, self._acc(xt), N, xt.H, xt.W, xt.C, out.H, out.W)
+                self._irb_backward(P, self._irb_dw[op])
+            elif op.kind in CONV_KINDS:
+                (self._conv_backward_bf16 if self.bf16 else self._conv_backward)(P, op)
             else:
-                raise NotImplementedError(k)
-        if self._bwd_pending:
+                arm = getattr(self, '_backward_' + op.kind, None)
+                if arm is None:
+                    raise NotImplementedError(op.kind)
+                arm(P, op)
+        if T.pending:
             self._flush_bn_backward(P)
         self._flush_deferred(P)
         self._reduce_pending(P)
@@ -1654,13 +1404,329 @@ class Executor:
             P.py(self.dist.wait_all)
         return P
 
-    def _irb_region(self, op):
-        nb = self._slab_bytes(op)
-        ptr = self.slab_ws.data_ptr() + 4 * self._slab_off[0]
-        self._slab_off[0] += ((nb + 255) // 256 * 256) // 4
-        return ptr, nb
+    def _begin_backward(self, T):
+        """what one backward trace decides up front: the BatchNorms whose backward sums ride on a data gradient, how weight
+        gradients are issued (deferred, as slabs) and the workspaces that takes.  -> the gradient bucket edges"""
+        T.ws, T.wsb = self.workspace.data_ptr(), self.workspace.numel() * 4
+        # data parallel: the flat gradient buffer is produced back to front; each finished bucket is
+        # all-reduced on the side stream while the remaining backward kernels run
+        bucket_edges = self._bucket_edges() if self.dist is not None else {}
+        # SyncBatchNorm: a layer's weight gradient feeds nothing in the backward chain, so it is held back and
+        # issued while the NEXT BatchNorm's statistics all-reduce is on the wire (hides the collective's latency)
+        T.defer = self.sync_bn
+        T.fuse = self._bn_fusion_map()
+        if self.bf16:
+            # bf16: the pointwise GEMMs can carry the sums (dl3p_pwconv_bwd_data_bn_bf16, more than 64 rows), the depthwise
+            # kernels cannot.  Opt-in: measured slower than the separate reduce pass (the epilogue meets z in 8-byte pieces:
+            # MobileNetV2 513x513 batch 16 12.37 against 11.83 ms, MobileNetV3-Large 1024x2048 batch 1 6.92 against 6.86)
+            T.fuse = {c: b for c, b in T.fuse.items() if c.kind == 'conv_pw' and self._rows(c) > 64
+                      and os.environ.get('DL3P_BF16_FUSE_BN_BWD', '0') == '1'}
+        T.stage_off = self._sync_total
+        T.readers = self._bn_readers()
+        T.bn_of = {id(o.z): o for o in self.g.ops if o.kind == 'bn'}
+        T.alias_ok = os.environ.get('DL3P_GRAD_ALIAS', '1') != '0'
+        # BatchNorm -> residual Add -> pointwise conv: the conv's data gradient is the last writer of d/d(Add output), which
+        # IS the gradient of the BatchNorm output, so it carries that BatchNorm's backward sums too (no bn_bwd_reduce pass)
+        T.fuse_add = self._bn_fusion_through_adds(T.readers) if not self.bf16 else {}
+        # the weight-gradient kernels leave their (fp32) slabs in per-layer regions of one buffer and ONE pair of launches
+        # reduces them all (dl3p_reduce_rows_batched; 65 reduce launches of 5-13 us each otherwise) -- at the end of
+        # backward on one GPU, per gradient bucket under data parallelism (in front of the bucket's all-reduce).  Same
+        # per-element arithmetic as the per-layer reduction, whichever way the jobs are grouped.
+        T.batch = os.environ.get('DL3P_BATCHED_WGRAD', '1') != '0'
+        T.batch_wgrad = T.batch and not T.defer
+        if T.batch_wgrad and not self.bf16:
+            need = max([self._rows(op) * (op.cout if op.kind == 'conv_pw' else op.c) for op in self.g.ops
+                        if op.kind in ('conv_pw', 'conv_dw') and op not in self._irb_expand] or [0])
+            T.dz_scratch = torch.zeros(need + 64, **self.f32)      # dz of the layer whose weight gradient just ran
+        if T.batch:
+            slab_need = 0
+            for op in self.g.ops:
+                if op.kind in CONV_KINDS and op.layer.trainable and self._slab_bytes(op):
+                    slab_need += (self._slab_bytes(op) + 255) // 256 * 256
+            T.slab_ws = torch.zeros(slab_need // 4 + 64, **self.f32) if slab_need else None
+        return bucket_edges
 
-    def _irb_backward(self, P, rec, fuse, fuse_add, bn_done, batch):
+    def _wgrad(self, P, fn, *args):
+        """issue a weight-gradient launch, or hold it back for the next _flush_deferred (SyncBatchNorm)"""
+        if self._bt.defer:
+            self._bt.deferred.append((fn, args, P.ctx))
+        else:
+            P.k(fn, *args)
+
+    def _slab_region(self, nbytes):
+        """the next region of slab_ws (regions are carved in trace order, 256-byte aligned)"""
+        T = self._bt
+        region = T.slab_ws.data_ptr() + 4 * T.slab_off
+        T.slab_off += ((nbytes + 255) // 256 * 256) // 4
+        return region
+
+    def _wgrad_slabs(self, P, fn, n, dst, nbytes, before, after, up=None):
+        """fn(*before, region, bytes, &rows, *after): a weight gradient that leaves its slabs for the batched reduction into the n
+        floats at dst; up: the arguments of the dl3p_dw_upsampled_input call that describes this launch's input (a conv that
+        absorbed its resize)"""
+        T, L = self._bt, self.L
+        region = self._slab_region(nbytes)
+
+        def issue(P2):
+            rows = ctypes.c_int(0)
+            if up is not None:
+                P2.k(L.dw_upsampled_input, *up)
+            P2.k(fn, *before, region, nbytes, ctypes.byref(rows), *after)
+            T.jobs.append((region, dst, rows.value, n))
+        if T.defer:
+            T.deferred.append((issue, None, P.ctx))      # runs at the next _flush_deferred, like the plain ones
+        else:
+            issue(P)
+
+    def _backward_bn(self, P, op, later):
+        T = self._bt
+        if not op.z.requires_grad or op in T.bn_done:
+            return
+        self._bn_backward_done(P, op)
+        if self.sync_bn and op.bn.layer.trainable:
+            # other BatchNorms whose gradient is complete already (every reader of their output has been
+            # processed: the ASPP branches behind concat_projection, a shortcut beside its residual branch):
+            # take their local sums now, so that one all-reduce serves them all
+            for op2 in later:
+                if (op2.kind == 'bn' and op2 not in T.bn_done and op2.z.requires_grad and op2.bn.layer.trainable
+                        and T.readers.get(op2) and T.readers[op2] <= T.processed and op2 not in T.fuse.values()):
+                    self._bn_backward_done(P, op2)
+
+    def _bn_backward_done(self, P, bn_op, fused_rows=None):
+        """issue this BatchNorm's backward under its own label and mark it done"""
+        with P.at(_op_label(bn_op)):
+            self._bn_backward(P, bn_op, fused_rows=fused_rows)
+        self._bt.bn_done.add(bn_op)
+
+    def _front_sums_done(self, P, front, front_add, rows):
+        """a data gradient left `rows` partial rows of the backward sums of the BatchNorm in front of its conv: one that the conv
+        reads directly (front, sums in self.partials) is finalised and applied now; one behind a residual Add (front_add, sums in
+        self.partials2) picks them up when the loop reaches it (_bn_backward)"""
+        if front is not None:
+            self._bn_backward_done(P, front, fused_rows=rows)
+        elif front_add is not None:
+            self._bt.presums[front_add] = rows
+
+    def _conv_backward(self, P, op):
+        """fp32 conv: the data gradient FIRST where it forms dz itself (the folded BatchNorm apply), the weight gradient (as slabs
+        or plain), then the data gradient, with the backward sums of the BatchNorm in front of the conv where they ride on it"""
+        T, out, xt = self._bt, op.out, op.x.tensor
+        dz, lddz = self.tptr(out, True), out.ld
+        need_gx = xt.requires_grad or xt.root.requires_grad
+        sums_left = None
+        if op.kind == 'conv_pw' and out.id in T.folded_dg:
+            dz, lddz, sums_left = self._dgrad_folded(P, op)
+        if op.layer.trainable and T.batch and self._slab_bytes(op):
+            dz, lddz = self._wgrad_slab(P, op, dz, lddz, need_gx)
+        elif op.layer.trainable:
+            self._wgrad_plain(P, op, dz, lddz)
+        if sums_left is not None:
+            # (the data gradient ran in front of the weight gradient; what is left is the BatchNorm in front of the conv)
+            self._front_sums_done(P, *sums_left)
+        elif need_gx:
+            self._dgrad(P, op, dz, lddz)
+
+    def _dgrad_folded(self, P, op):
+        """data gradient of a pointwise conv that forms dz = BatchNorm-backward apply of (g, z) in its staging pass and leaves it
+        for the weight gradient.  -> (dz, lddz, (front, front_add, partial rows of the sums it left))"""
+        f = self._bt.folded_dg.pop(op.out.id)
+        gp, ldg, acc = self._gbuf_acc(op.x)
+        wsp, pitch = self.store.sb_ptr(op, False)
+        front, front_add = self._front_bn(op)
+        rows = ctypes.c_int(0)
+        sums = self._front_sums(front or front_add, self.partials if front is not None else self.partials2, rows)
+        P.k(self.L.pwconv_bwd_data_sb_apply, *f, wsp, pitch, gp, ldg, acc, *self._mkn(op), *sums)
+        return f.dz, f.lddz, (front, front_add, rows.value)
+
+    def _wgrad_slab(self, P, op, dz, lddz, need_gx):
+        """weight gradient left as slabs (_slab_bytes(op) > 0).  Where the BatchNorm behind the conv folded its apply pass in
+        (_folds_apply), the kernel forms dz from (g, z) and hands it on in dz_scratch.  -> (dz, lddz) the data gradient reads"""
+        T, L = self._bt, self.L
+        r = self._bwd_route(op)
+        x = self.vargs(op.x)
+        f = T.folded.pop(op.out.id, None)
+        if f is not None and r != R_STEM:
+            dz, lddz = (T.dz_scratch.data_ptr(), op.cout if r == R_PW else op.c) if need_gx else (None, 0)
+        bn = f is not None
+        before = (*x, *f, dz, lddz) if bn else (*x, dz, lddz)
+        if r == R_PW:
+            fn, n, after = (L.pwconv_bwd_weight_slabs_bn if bn else L.pwconv_bwd_weight_slabs), op.cin * op.cout, self._mkn(op)
+        elif r == R_DW:
+            fn, n, after = (L.dwconv2d_bwd_weight_slabs_bn if bn else L.dwconv2d_bwd_weight_slabs), op.k * op.k * op.c, self._geo(op, 'dw')
+        elif r == R_STEM:
+            # the stem has no data gradient: dz = BatchNorm-backward apply of (g, z) is formed in the weight gradient's
+            # staging pass and never written
+            fn, n, after = (L.stem_conv_bwd_weight_slabs_bn if bn else L.stem_conv_bwd_weight_slabs), 28 * op.cout, self._geo(op, 'stem')
+            before = (x[0], x[1], *f) if bn else (x[0], x[1], dz, lddz)
+        elif r == R_NARROW:
+            fn, n, after = L.conv_narrow_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, self._geo(op, 'io')
+        else:
+            fn, n, after = L.conv2d_gemm_bwd_weight_slabs, op.k * op.k * op.cin * op.cout, self._geo(op, 'dense')
+        self._wgrad_slabs(P, fn, n, self.store.ptr(op.w, self.store.G), self._slab_bytes(op), before, after, up=self._up_args(op))
+        return dz, lddz
+
+    def _wgrad_plain(self, P, op, dz, lddz):
+        """weight gradient reduced by its own launch into the flat gradient buffer (through the shared workspace)"""
+        T, L, st = self._bt, self.L, self.store
+        r = self._bwd_route(op)
+        x = self.vargs(op.x)
+        gw = st.ptr(op.w, st.G)
+        b = getattr(op, 'b', None)
+        gb = st.ptr(b, st.G) if b else None
+        if r == R_PW:
+            self._wgrad(P, L.pwconv_bwd_weight, *x, dz, lddz, gw, gb, T.ws, T.wsb, *self._mkn(op))
+        elif r == R_DW:
+            if self._up_args(op) is not None:
+                self._wgrad(P, L.dw_upsampled_input, *self._up_args(op))
+            self._wgrad(P, L.dwconv2d_bwd_weight, *x, dz, lddz, gw, T.ws, T.wsb, *self._geo(op, 'dw'))
+        elif r == R_STEM:
+            self._wgrad(P, L.stem_conv_bwd_weight, x[0], x[1], dz, lddz, gw, T.ws, T.wsb, *self._geo(op, 'stem'))
+        elif r == R_NARROW:
+            self._wgrad(P, L.conv_narrow_bwd_weight, *x, dz, lddz, gw, T.ws, T.wsb, *self._geo(op, 'io'))
+        elif r == R_GEMM:
+            self._wgrad(P, L.conv2d_gemm_bwd_weight, *x, dz, lddz, gw, gb, T.ws, T.wsb, *self._geo(op, 'dense'))
+        else:
+            self._wgrad(P, L.pwconv_bwd_weight, self.tptr(op.col), op.col.ld, None, None, ACT_NONE, dz, lddz, gw, gb, T.ws, T.wsb,
+                        *self._mkn(op))
+
+    def _dgrad(self, P, op, dz, lddz):
+        """data gradient of an fp32 conv.  A pointwise or depthwise conv that is the last writer of the gradient of a BatchNorm's
+        output (_front_bn) leaves that BatchNorm's backward sums beside it"""
+        L, st = self.L, self.store
+        r = self._bwd_route(op)
+        g = self._gbuf_acc(op.x)
+        front, front_add = self._front_bn(op)
+        bn_front = front or front_add
+        rows = ctypes.c_int(0)
+        sums = self._front_sums(bn_front, self.partials if front is not None else self.partials2, rows)
+        if r == R_PW and self._use_sb(op, False, bn_front is not None):
+            P.k(L.pwconv_bwd_data_sb, dz, lddz, *st.sb_ptr(op, False), *g, *self._mkn(op), *sums)
+        elif r == R_PW and bn_front is not None:
+            P.k(L.pwconv_bwd_data_bn, dz, lddz, st.ptr(op.w), *g, *self._mkn(op), *sums)
+        elif r == R_PW:
+            P.k(L.pwconv_bwd_data, dz, lddz, st.ptr(op.w), *g, *self._mkn(op))
+        elif r == R_DW and bn_front is not None:
+            P.k(L.dwconv2d_bwd_data_bn, dz, lddz, st.ptr(op.w), *g, *self._geo(op, 'dw'), *sums)
+        elif r == R_DW:
+            P.k(L.dwconv2d_bwd_data, dz, lddz, st.ptr(op.w), *g, *self._geo(op, 'dw'))
+        elif r == R_NARROW:
+            P.k(L.conv_narrow_bwd_data, dz, lddz, st.ptr(op.w), *g, *self._geo(op, 'io'))
+        elif r == R_GEMM and op.k > 1:
+            wd = self.dense_wd[id(op)]
+            P.k(L.conv2d_gemm_dgrad_weights, st.ptr(op.w), wd.data_ptr(), op.k, op.cin, op.cout)
+            if self._use_sb_dense(op, 2):
+                # the re-laid kernel [Cin][k k Cout] split into its three bf16 planes (a few hundred KB), then the
+                # data gradient on the bf16 matrix pipe
+                kd = op.k * op.k * op.cout
+                pitch = (kd + 31) // 32 * 32
+                sp3 = self.dense_wd_sb.get(id(op))
+                if sp3 is None:
+                    sp3 = self.dense_wd_sb[id(op)] = (torch.zeros(3 * op.cin * pitch, dtype=torch.int16, device=self.dev),
+                                                      torch.tensor([[0, op.cin, kd, kd, 0, pitch]], dtype=torch.int64, device=self.dev))
+                P.k(L.split_bf16x3_batch, wd.data_ptr(), sp3[0].data_ptr(), sp3[1].data_ptr(), 1)
+                P.k(L.conv2d_gemm_bwd_data_sb, dz, lddz, sp3[0].data_ptr(), pitch, *g, *self._geo(op, 'dense'))
+            else:
+                P.k(L.conv2d_gemm_bwd_data, dz, lddz, wd.data_ptr(), *g, *self._geo(op, 'dense'))
+        else:
+            # (im2col route, and the strided 1x1 convs of the implicit GEMM: _alloc's grad_cols)
+            # d/d(im2col matrix) by the GEMM, then the transposed gather back onto the input pixels
+            P.k(L.pwconv_bwd_data, dz, lddz, st.ptr(op.w), self.tptr(op.col, True), op.col.ld, 0, *self._mkn(op))
+            P.k(L.col2im, self.tptr(op.col, True), op.col.ld, *g, *self._geo(op, 'dw'))
+        self._front_sums_done(P, front, front_add, rows.value)
+
+    def _backward_conv_deconv(self, P, op):
+        L, st, T = self.L, self.store, self._bt
+        xt, out = op.x.tensor, op.out
+        dz, lddz = self.tptr(out, True), out.ld
+        if op.layer.trainable:
+            self._wgrad(P, L.deconv2x2_bwd_weight, *self.vargs(op.x), dz, lddz, st.ptr(op.w, st.G),
+                        st.ptr(op.b, st.G) if op.b else None, T.ws, T.wsb, *self._geo(op, 'io'))
+        if xt.requires_grad or xt.root.requires_grad:
+            P.k(L.deconv2x2_bwd_data, dz, lddz, st.ptr(op.w), *self._gbuf_acc(op.x), *self._geo(op, 'io'))
+
+    def _backward_materialize(self, P, op):
+        T, out = self._bt, op.out
+        mask_bwd = self.L.scale_mask_bwd_bf16 if self.bf16 else self.L.scale_mask_bwd
+        gt, ldt = self.tptr(out, True), out.ld
+        M = self.N * out.H * out.W
+        if op.x.tensor.requires_grad or op.x.tensor.root.requires_grad:
+            xb = T.bn_of.get(id(op.x.tensor)) if op.x.bn is not None else None
+            if (T.alias_ok and xb is not None and float(op.rate) == 0.0 and getattr(op.x, 'view_grad', None) is None
+                    and op.x.tensor.C == out.C and T.readers.get(xb) == {op} and op.x.tensor.id not in T.written
+                    and (op.x.tensor.base is None or op.x.tensor.base.id not in T.written)):
+                # a residual Add hands its gradient to the BatchNorm branch unchanged: that BatchNorm's backward
+                # reads it where it is (no copy into the branch's own buffer, one launch less per Add)
+                T.galias[op.x.tensor.id] = (gt, ldt)
+                T.written.add(op.x.tensor.id)
+            else:
+                gp, ldg, keyt = self._gbuf(op.x)
+                P.k(mask_bwd, gt, ldt, float(op.rate), self._dropout_seed(op), self.step.data_ptr(), gp, ldg, self._acc(keyt),
+                    M, out.C)
+        if op.r is not None and (op.r.tensor.requires_grad or op.r.tensor.root.requires_grad):
+            rt = op.r.tensor
+            rb = T.bn_of.get(id(rt)) if op.r.bn is not None else None
+            fresh = (T.alias_ok and getattr(op.r, 'view_grad', None) is None and rt.C == out.C
+                     and rt.id not in T.written and (rt.base is None or rt.base.id not in T.written))
+            if fresh and rb is not None and T.readers.get(rb) == {op}:
+                T.galias[rt.id] = (gt, ldt)        # the other branch is a BatchNorm too (Xception shortcut)
+                T.written.add(rt.id)
+            elif (fresh and (op.r.is_plain or rb is not None) and rt.base is None and out.base is None and rt.ld == out.ld
+                  and rt.id in self.grad and out.id in self.grad
+                  and self.grad[rt.id].numel() == self.grad[out.id].numel()):
+                # the identity branch: d/d(r) starts as d/d(out) and only ever gains contributions that are issued
+                # after every reader of d/d(out) (the producer of r precedes this Add's other branch): the two
+                # gradients share one buffer from here on, no copy
+                self.grad[rt.id] = self.grad[out.id]
+                T.written.add(rt.id)
+            else:
+                gp, ldg, keyt = self._gbuf(op.r)
+                P.k(mask_bwd, gt, ldt, 0.0, 0, None, gp, ldg, self._acc(keyt), M, out.C)
+
+    def _backward_se_mul(self, P, op):
+        out = op.out
+        xp, ldx, sp, hp, act = self.vargs(op.x)
+        s_ptr, lds, _, _, sact = self.vargs(op.s)
+        gp, ldg, keyx = self._gbuf(op.x)
+        gsp, ldgs, keys = self._gbuf(op.s)
+        assert self._acc(keys) == 0, 'SE scale gradient has a single producer'
+        P.k(self.L.scale_bcast_bwd_bf16 if self.bf16 else self.L.scale_bcast_bwd, self.tptr(out, True), out.ld, xp, ldx, sp, hp,
+            act, s_ptr, lds, sact, gp, ldg,
+            self._acc(keyx), gsp, ldgs, self.N, out.H * out.W, out.C, self.pool_ws.data_ptr(), self.pool_wsb)
+
+    def _backward_maxpool(self, P, op):
+        L, out, xt = self.L, op.out, op.x.tensor
+        g = self._gbuf_acc(op.x)
+        geo = (self.N, xt.H, xt.W, xt.C, op.k, op.stride, op.pad_t, op.pad_l, op.Ho, op.Wo)
+        if self.bf16:
+            P.k(L.maxpool2d_bwd_bf16, self.tptr(out, True), out.ld, self._pool_arg[op].data_ptr(), *g, *geo)
+        else:
+            P.k(L.maxpool2d_bwd, *self.vargs(op.x), self.tptr(out, True), out.ld, self._pool_arg[op].data_ptr(), *g, *geo)
+
+    def _backward_avgpool(self, P, op):
+        # d/d(activated input); the producer's BatchNorm backward applies act' (as behind 'maxpool')
+        out, xt = op.out, op.x.tensor
+        P.k(self.L.avgpool2d_bwd_bf16 if self.bf16 else self.L.avgpool2d_bwd, self.tptr(out, True), out.ld,
+            *self._gbuf_acc(op.x), self.N, xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
+
+    def _backward_gap(self, P, op):
+        out, xt = op.out, op.x.tensor
+        P.k(self.L.global_avgpool_bwd_bf16 if self.bf16 else self.L.global_avgpool_bwd, self.tptr(out, True), out.ld,
+            *self._gbuf_acc(op.x), self.N, xt.H * xt.W, xt.C)
+
+    def _backward_broadcast(self, P, op):
+        # gradient w.r.t. the (lazy) 1x1 value = sum over the pixels it was broadcast to
+        out, xt = op.out, op.x.tensor
+        assert self._acc(xt) == 0
+        P.k(self.L.global_avgpool_fwd_bf16 if self.bf16 else self.L.global_avgpool_fwd, self.tptr(out, True), out.ld, None, None,
+            ACT_NONE, self.tptr(xt, True), xt.ld, float(out.H * out.W), self.N, out.H * out.W, out.C,
+            self.pool_ws.data_ptr(), self.pool_wsb)
+
+    def _backward_resize(self, P, op):
+        out, xt = op.out, op.x.tensor
+        P.k(self.L.resize_bilinear_bwd_bf16 if self.bf16 else self.L.resize_bilinear_bwd, self.tptr(out, True), out.ld,
+            self.tptr(xt, True), xt.ld, self._acc(xt), self.N, xt.H, xt.W, xt.C, out.H, out.W)
+
+    def _irb_backward(self, P, rec):
         """backward of a fused inverted-residual block, issued where the loop reaches its depthwise conv: pass A (depthwise kernel
         gradient + the expand BatchNorm's backward sums), that BatchNorm's finalize, pass B (expand kernel gradient + gradient of
         the block input, with the backward sums of a BatchNorm in front of the block where the unfused path would carry them).
@@ -1668,137 +1734,92 @@ class Executor:
         triggers when it reaches the expand conv"""
         e, b, d = rec
         L, st = self.L, self.store
-        if not batch:
+        if not self._bt.batch:
             raise RuntimeError('fused inverted-residual blocks leave their weight gradients as slabs (DL3P_BATCHED_WGRAD=0 and a '
                                'fused block in the same executor: _find_irb should not have fused)')
         aux = self.bn_aux[b.bn]
         dz, lddz = self.tptr(d.out, True), d.out.ld
-        ctx = P.ctx
-        rg, nb = self._irb_region(d)
+        nb = self._slab_bytes(d)
+        rg = self._slab_region(nb)
         rows_a = ctypes.c_int(0)
         P.k(L.irb_bwd_sums, *self._irb_args(rec), aux['mean'].data_ptr(), aux['invstd'].data_ptr(), st.ptr(d.w), dz, lddz, rg, nb,
             ctypes.byref(rows_a), self.partials.data_ptr(), *self._irb_geo(rec), tag=d.name)
-        self._jobs.append((rg, st.ptr(d.w, st.G), rows_a.value, d.k * d.k * d.c))
-        P.ctx = _op_label(b)
-        self._bn_backward(P, b, fused_rows=rows_a.value)
-        bn_done.add(b)
+        self._bt.jobs.append((rg, st.ptr(d.w, st.G), rows_a.value, d.k * d.k * d.c))
+        self._bn_backward_done(P, b, fused_rows=rows_a.value)
         if not self.sync_bn:
             self._irb_pass_b(P, rec)
-        P.ctx = ctx
 
     def _irb_pass_b(self, P, rec):
         e, b, d = rec
         L, st = self.L, self.store
-        fuse, fuse_add, bn_done = self._bwd_ctx
         aux = self.bn_aux[b.bn]
         mean, invstd, coef = aux['mean'].data_ptr(), aux['invstd'].data_ptr(), aux['coef'].data_ptr()
         dz, lddz = self.tptr(d.out, True), d.out.ld
-        ctx = P.ctx
-        P.ctx = _op_label(e)
         xt = e.x.tensor
-        need_gx = xt.requires_grad or xt.root.requires_grad
-        gp = ldg = None
-        acc = 0
-        front = front_add = None
-        if need_gx:
-            gp, ldg, keyt = self._gbuf(e.x)
-            acc = self._acc(keyt)
-            front = fuse.get(e) if (e in fuse and fuse[e].z.requires_grad) else None
-            front_add = fuse_add.get(e) if (front is None and e in fuse_add and fuse_add[e].z.requires_grad) else None
-        bn_front = front or front_add
-        fargs = (None, 0, None, None, ACT_NONE, None, None, None)
-        if bn_front is not None:
-            bnf = bn_front.bn
-            auxf = self.bn_aux[bnf]
-            part_f = self.partials if front is not None else self.partials2
-            fargs = (self.tptr(bn_front.z), bn_front.z.ld, self.gscale[bnf.group.id].data_ptr() + 4 * bnf.offset,
-                     self.gshift[bnf.group.id].data_ptr() + 4 * bnf.offset, bnf.act, auxf['mean'].data_ptr(),
-                     auxf['invstd'].data_ptr(), part_f.data_ptr())
-        rg, nb = self._irb_region(e)
-        rows_b = ctypes.c_int(0)
-        P.k(L.irb_bwd_data, *self._irb_args(rec), mean, invstd, coef, st.ptr(d.w), dz, lddz, rg, nb, ctypes.byref(rows_b), gp,
-            ldg or 0, acc, *fargs, *self._irb_geo(rec), tag='pw:' + e.name)
-        self._jobs.append((rg, st.ptr(e.w, st.G), rows_b.value, e.cin * e.cout))
-        if front is not None:
-            P.ctx = _op_label(front)
-            self._bn_backward(P, front, fused_rows=rows_b.value)
-            bn_done.add(front)
-        elif front_add is not None:
-            self._presums[front_add] = rows_b.value
-        P.ctx = ctx
+        g, front, front_add = (None, 0, 0), None, None
+        with P.at(_op_label(e)):
+            if xt.requires_grad or xt.root.requires_grad:
+                g = self._gbuf_acc(e.x)
+                front, front_add = self._front_bn(e)
+            nb = self._slab_bytes(e)
+            rg = self._slab_region(nb)
+            rows_b = ctypes.c_int(0)
+            # (the sums in front come in as many partial rows as the slabs: the group goes without its row count)
+            sums = self._front_sums(front or front_add, self.partials if front is not None else self.partials2, rows_b)[:8]
+            P.k(L.irb_bwd_data, *self._irb_args(rec), mean, invstd, coef, st.ptr(d.w), dz, lddz, rg, nb, ctypes.byref(rows_b), *g,
+                *sums, *self._irb_geo(rec), tag='pw:' + e.name)
+            self._bt.jobs.append((rg, st.ptr(e.w, st.G), rows_b.value, e.cin * e.cout))
+            self._front_sums_done(P, front, front_add, rows_b.value)
 
-    def _conv_backward_bf16(self, P, op, wgrad, ws, wsb, wgrad_slabs=None, fused_bn=None):
-        """weight and data gradient of one conv on the bf16 path; `fused_bn`: the 'bn' op whose backward sums the pointwise
-        data gradient carries (its finalize + apply are issued right behind it)"""
-        L, N, st, k = self.L, self.N, self.store, op.kind
-        G, out = st.G, op.out
-        xp, ldx, sp, hp, act = self.vargs(op.x)
-        xt = op.x.tensor
+    def _conv_backward_bf16(self, P, op):
+        """weight and data gradient of one conv on the bf16 path; where the pointwise data gradient carries the backward sums of
+        the BatchNorm in front of the conv (_front_bn), that BatchNorm's finalize + apply are issued right behind it"""
+        T, L, st = self._bt, self.L, self.store
+        out, xt = op.out, op.x.tensor
+        r = self._bwd_route(op)
+        x = self.vargs(op.x)
         dz, lddz, dzf = self.tptr(out, True), out.ld, self._is_f32(out)
-        need_gx = xt.requires_grad or xt.root.requires_grad
-        M = N * op.Ho * op.Wo
+        mkn = self._mkn(op) if r != R_DW else None
+        front, _ = self._front_bn(op)
         if op.layer.trainable:
-            gw = st.ptr(op.w, G)
-            gb = st.ptr(op.b, G) if getattr(op, 'b', None) else None
-            nb = self._slab_bytes(op) if wgrad_slabs else 0
-            if nb and k == 'conv_dw':
-                wgrad_slabs(L.dwconv2d_bwd_weight_slabs_bf16, op.k * op.k * op.c, gw, nb, (xp, ldx, sp, hp, act, dz, lddz),
-                            (N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo))
-            elif nb and k == 'conv_pw':
-                wgrad_slabs(L.pwconv_bwd_weight_slabs_bf16, op.cin * op.cout, gw, nb, (xp, ldx, sp, hp, act, dz, lddz, dzf),
-                            (M, op.cin, op.cout))
+            gw = st.ptr(op.w, st.G)
+            gb = st.ptr(op.b, st.G) if getattr(op, 'b', None) else None
+            nb = self._slab_bytes(op) if T.batch else 0
+            # (a dense conv: the GEMM over its im2col matrix)
+            a = x if r in (R_PW, R_DW) else (self.tptr(op.col), op.col.ld, None, None, ACT_NONE)
+            if nb and r == R_DW:
+                self._wgrad_slabs(P, L.dwconv2d_bwd_weight_slabs_bf16, op.k * op.k * op.c, gw, nb, (*x, dz, lddz), self._geo(op, 'dw'))
             elif nb:
-                wgrad_slabs(L.pwconv_bwd_weight_slabs_bf16, op.kp * op.cout, gw, nb,
-                            (self.tptr(op.col), op.col.ld, None, None, ACT_NONE, dz, lddz, dzf), (M, op.kp, op.cout))
-            elif k == 'conv_pw':
-                wgrad(L.pwconv_bwd_weight_bf16, xp, ldx, sp, hp, act, dz, lddz, dzf, gw, gb, ws, wsb, M, op.cin, op.cout)
-            elif k == 'conv_dw':
-                wgrad(L.dwconv2d_bwd_weight_bf16, xp, ldx, sp, hp, act, dz, lddz, gw, ws, wsb, N, xt.H, xt.W, op.c, op.k,
-                      op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
+                self._wgrad_slabs(P, L.pwconv_bwd_weight_slabs_bf16, mkn[1] * mkn[2], gw, nb, (*a, dz, lddz, dzf), mkn)
+            elif r == R_DW:
+                self._wgrad(P, L.dwconv2d_bwd_weight_bf16, *x, dz, lddz, gw, T.ws, T.wsb, *self._geo(op, 'dw'))
             else:
-                wgrad(L.pwconv_bwd_weight_bf16, self.tptr(op.col), op.col.ld, None, None, ACT_NONE, dz, lddz, dzf, gw, gb,
-                      ws, wsb, M, op.kp, op.cout)
-        if not need_gx:
-            return
-        gp, ldg, keyt = self._gbuf(op.x)
-        acc = self._acc(keyt)
-        self._conv_dgrad_bf16(P, op, fused_bn, dz, lddz, dzf, gp, ldg, acc, M)
+                self._wgrad(P, L.pwconv_bwd_weight_bf16, *a, dz, lddz, dzf, gw, gb, T.ws, T.wsb, *mkn)
+        if xt.requires_grad or xt.root.requires_grad:
+            self._dgrad_bf16(P, op, r, front, dz, lddz, dzf, mkn)
+        if front is not None:
+            T.bn_done.add(front)
 
-    def _conv_dgrad_bf16(self, P, op, fused_bn, dz, lddz, dzf, gp, ldg, acc, M):
-        L, N, st, k = self.L, self.N, self.store, op.kind
-        xt = op.x.tensor
-        if k == 'conv_pw' and fused_bn is not None and not dzf:
+    def _dgrad_bf16(self, P, op, r, front, dz, lddz, dzf, mkn):
+        L, st = self.L, self.store
+        g = self._gbuf_acc(op.x)
+        if r == R_PW and front is not None and not dzf:
             # the BatchNorm-backward sums of the BatchNorm behind this gradient ride on the data gradient (dl3p_pwconv_bwd_data_bn)
-            bn = fused_bn.bn
-            aux = self.bn_aux[bn]
             rows = ctypes.c_int(0)
-            P.k(L.pwconv_bwd_data_bn_bf16, dz, lddz, st.ptr(op.w, st.Pb), gp, ldg, acc, M, op.cin, op.cout,
-                self.tptr(fused_bn.z), fused_bn.z.ld, self.gscale[bn.group.id].data_ptr() + 4 * bn.offset,
-                self.gshift[bn.group.id].data_ptr() + 4 * bn.offset, bn.act, aux['mean'].data_ptr(),
-                aux['invstd'].data_ptr(), self.partials.data_ptr(), ctypes.byref(rows))
-            ctx = P.ctx
-            P.ctx = _op_label(fused_bn)
-            self._bn_backward(P, fused_bn, fused_rows=rows.value)
-            P.ctx = ctx
-        elif k == 'conv_pw':
-            if fused_bn is not None:          # (an fp32 gradient operand: the kernel with the sums takes bf16 only)
-                ctx = P.ctx
-                P.k(L.pwconv_bwd_data_bf16, dz, lddz, dzf, st.ptr(op.w, st.Pb), gp, ldg, acc, M, op.cin, op.cout)
-                P.ctx = _op_label(fused_bn)
-                self._bn_backward(P, fused_bn)
-                P.ctx = ctx
-                return
-            P.k(L.pwconv_bwd_data_bf16, dz, lddz, dzf, st.ptr(op.w, st.Pb), gp, ldg, acc, M, op.cin, op.cout)
-        elif k == 'conv_dw':
-            P.k(L.dwconv2d_bwd_data_bf16, dz, lddz, st.ptr(op.w, st.Pb), gp, ldg, acc, N, xt.H, xt.W, op.c, op.k, op.stride,
-                op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo)
+            P.k(L.pwconv_bwd_data_bn_bf16, dz, lddz, st.ptr(op.w, st.Pb), *g, *mkn,
+                *self._front_sums(front, self.partials, rows))
+            self._bn_backward_done(P, front, fused_rows=rows.value)
+        elif r == R_PW:
+            P.k(L.pwconv_bwd_data_bf16, dz, lddz, dzf, st.ptr(op.w, st.Pb), *g, *mkn)
+            if front is not None:          # (an fp32 gradient operand: the kernel with the sums takes bf16 only)
+                self._bn_backward_done(P, front)
+        elif r == R_DW:
+            P.k(L.dwconv2d_bwd_data_bf16, dz, lddz, st.ptr(op.w, st.Pb), *g, *self._geo(op, 'dw'))
         else:
             # dense k x k conv (Xception's entry_flow_conv1_2, ResNet50's 3x3 convs): d/d(im2col matrix) by the GEMM, then the
             # transposed gather back onto the input pixels -- the route of the forward (im2col_bf16 + GEMM), mirrored
-            P.k(L.pwconv_bwd_data_bf16, dz, lddz, dzf, st.ptr(op.w, st.Pb), self.tptr(op.col, True), op.col.ld, 0, M, op.kp,
-                op.cout)
-            P.k(L.col2im_bf16, self.tptr(op.col, True), op.col.ld, gp, ldg, acc, N, xt.H, xt.W, op.cin, op.k, op.stride, op.rate,
-                op.pad_t, op.pad_l, op.Ho, op.Wo)
+            P.k(L.pwconv_bwd_data_bf16, dz, lddz, dzf, st.ptr(op.w, st.Pb), self.tptr(op.col, True), op.col.ld, 0, *mkn)
+            P.k(L.col2im_bf16, self.tptr(op.col, True), op.col.ld, *g, *self._geo(op, 'dw'))
 
     def _use_sb(self, op, fwd, stats):
         """does this pointwise conv run on the split-bf16 GEMM (forward / data-gradient role)?  Only where the tiled kernel
@@ -1846,20 +1867,6 @@ class Executor:
         if role != 2:
             self._sb_used_f.add(op)          # the optimiser step refreshes this plane (_trace_sgd)
         return True
-
-    def _pw_dgrad_bn(self, P, op, dz, lddz, gp, ldg, acc, bn_op, partials, rows):
-        """data gradient of a pointwise conv + the BatchNorm-backward partial sums of the BatchNorm in front of it"""
-        st, L, bn = self.store, self.L, bn_op.bn
-        aux = self.bn_aux[bn]
-        M = self.N * op.Ho * op.Wo
-        bnargs = (self.tptr(bn_op.z), bn_op.z.ld, self.gscale[bn.group.id].data_ptr() + 4 * bn.offset,
-                  self.gshift[bn.group.id].data_ptr() + 4 * bn.offset, bn.act, aux['mean'].data_ptr(), aux['invstd'].data_ptr(),
-                  partials.data_ptr(), ctypes.byref(rows))
-        if self._use_sb(op, False, True):
-            wsp, pitch = st.sb_ptr(op, False)
-            P.k(L.pwconv_bwd_data_sb, dz, lddz, wsp, pitch, gp, ldg, acc, M, op.cin, op.cout, *bnargs)
-        else:
-            P.k(L.pwconv_bwd_data_bn, dz, lddz, st.ptr(op.w), gp, ldg, acc, M, op.cin, op.cout, *bnargs)
 
     def _bn_fusion_map(self):
         """{consumer conv op: 'bn' op} for every trainable BatchNorm whose output value is read FIRST (in graph order) by a
@@ -1920,43 +1927,40 @@ class Executor:
         return out
 
     def _flush_deferred(self, P):
-        ctx = P.ctx
-        for fn, args, c in self._deferred:
-            P.ctx = c
-            if args is None:
-                fn(P)                 # a slab-leaving weight gradient: launches and files its reduction job
-            else:
-                P.k(fn, *args)
-        self._deferred = []
-        P.ctx = ctx
+        T = self._bt
+        for fn, args, c in T.deferred:
+            with P.at(c):
+                if args is None:
+                    fn(P)             # a slab-leaving weight gradient: launches and files its reduction job
+                else:
+                    P.k(fn, *args)
+        T.deferred = []
 
     def _reduce_pending(self, P):
-        if getattr(self, '_jobs', None):
-            ctx = P.ctx
-            P.ctx = 'wgrad:reduce_all'
-            self._reduce_all(P, self._jobs)
-            del self._jobs[:]
-            P.ctx = ctx
+        T = self._bt
+        if T.jobs:
+            with P.at('wgrad:reduce_all'):
+                self._reduce_all(P, T.jobs)
+            del T.jobs[:]
 
     def _bucket_edges(self):
         edges, self._first_bucket_hi = bucket_edges(self.g, self.store.offset, self.store.total, self.dist.n_buckets)
         return edges
 
     def _bn_backward(self, P, op, fused_rows=None):
-        bn, L, st, N = op.bn, self.L, self.store, self.N
+        bn, L, st, N, T = op.bn, self.L, self.store, self.N, self._bt
         aux = self.bn_aux[bn]
         lp = {p.key: p for p in bn.layer.params}
         z = op.z
         M = N * z.H * z.W
-        sp = self.gscale[bn.group.id].data_ptr() + 4 * bn.offset
-        hp = self.gshift[bn.group.id].data_ptr() + 4 * bn.offset
+        sp, hp = self._bn_coeffs(bn)
         if op in self._irb_bn:              # (a fused block's expand output and its gradient have no buffers: sums in, triple out)
             g = ldg = dzo = lddzo = zp = ldz = None
         else:
             g, ldg = self.tptr(z, True), z.ld
             dzo, lddzo = g, ldg             # where dz goes (g itself unless the gradient is read from another buffer)
-            if z.id in getattr(self, '_galias', {}):
-                g, ldg = self._galias.pop(z.id)
+            if z.id in T.galias:
+                g, ldg = T.galias.pop(z.id)
             zp, ldz = self.tptr(z), z.ld
         mean, invstd, coef = aux['mean'].data_ptr(), aux['invstd'].data_ptr(), aux['coef'].data_ptr()
         frozen = not bn.layer.trainable
@@ -1965,8 +1969,8 @@ class Executor:
             P.k(L.bn_bwd_finalize, None, 0, None, bn.C, float(M), st.ptr(lp['gamma']), invstd, sp, 1, None, None, coef)
         else:
             part = self.partials.data_ptr()
-            if fused_rows is None and op in getattr(self, '_presums', {}):
-                fused_rows, part = self._presums.pop(op), self.partials2.data_ptr()
+            if fused_rows is None and op in T.presums:
+                fused_rows, part = T.presums.pop(op), self.partials2.data_ptr()
             rows = ctypes.c_int(fused_rows or 0)
             if fused_rows is None:      # (otherwise the producer of g already left the partial sums)
                 P.k(L.bn_bwd_reduce_bf16 if self.bf16 else L.bn_bwd_reduce, g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd,
@@ -1978,23 +1982,23 @@ class Executor:
                 # use the global sums: local sums into this BatchNorm's slice of the staging buffer, all-reduce +
                 # finalize + apply when the producer of z is reached (_flush_bn_backward), together with every other
                 # BatchNorm pending by then
-                off = self._bwd_stage_off
-                self._bwd_stage_off += 2 * bn.C
+                off = T.stage_off
+                T.stage_off += 2 * bn.C
                 P.k(L.bn_reduce_partials, part, rows.value, 2 * bn.C, self.sync_stage[off:].data_ptr())
-                self._bwd_pending.append((op, off, P.ctx))
-                self._sync_g[op] = (g, ldg)
+                T.pending.append((op, off, P.ctx))
+                T.sync_g[op] = (g, ldg)
                 return
         if not frozen and op in self._irb_bn:
             return                          # dl3p_irb_bwd_data forms dz from the coefficient triple while it recomputes the expand conv
         if not frozen and self._folds_apply_dgrad(op):
             # the conv that produced z forms dz while its DATA gradient stages its operand, writes it where the apply pass would
             # have, and its weight gradient (issued behind the data gradient for that) reads it there
-            self._folded_dg[z.id] = (g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd, coef, dzo, lddzo)
+            T.folded_dg[z.id] = FoldedDg(g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd, coef, dzo, lddzo)
             return
         if not frozen and self._folds_apply(op):
             # the conv that produced z forms dz inside its weight-gradient kernel and hands it to its data gradient
-            self._folded[z.id] = (g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd, coef)
-            self._dz_not_kept.add(z.root.id)
+            T.folded[z.id] = Folded(g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd, coef)
+            T.dz_not_kept.add(z.root.id)
             return
         P.k(L.bn_bwd_apply_bf16 if self.bf16 else L.bn_bwd_apply, g, ldg, zp, ldz, sp, hp, bn.act, mean, invstd, coef, dzo,
             lddzo, 0, M, bn.C)
@@ -2010,13 +2014,11 @@ class Executor:
         xt = conv.x.tensor
         if not (xt.requires_grad or xt.root.requires_grad):
             return False
-        M = self.N * conv.Ho * conv.Wo
-        # the launch this decides about (_trace_backward, `out.id in self._folded_dg`): with the sums of a BatchNorm in front of the
-        # conv (role 3) or without (role 2), the gradient written at the pitch of the buffer that collects d/d(conv input)
-        fuse, fuse_add, _ = self._bwd_ctx
-        front = fuse.get(conv) if (conv in fuse and fuse[conv].z.requires_grad) else None
-        if front is None and conv in fuse_add and fuse_add[conv].z.requires_grad:
-            front = fuse_add[conv]
+        M = self._rows(conv)
+        # the launch this decides about (_dgrad_folded): with the sums of a BatchNorm in front of the conv (role 3) or without
+        # (role 2), the gradient written at the pitch of the buffer that collects d/d(conv input)
+        front, front_add = self._front_bn(conv)
+        front = front or front_add
         vt = getattr(conv.x, 'view_grad', None)
         ldg = vt.ld if vt is not None else xt.ld
         if M * max(xt.ld, ldg, bn_op.z.ld, conv.cout, front.z.ld if front is not None else 0) * 4 >= 2 ** 32:
@@ -2030,7 +2032,7 @@ class Executor:
         statistics, weight gradient issued in line in front of the data gradient)"""
         conv = getattr(bn_op, 'producer', None)
         if (self.bf16 or self.sync_bn or self.dist is not None or conv is None or conv.kind not in ('conv_pw', 'conv_dw', 'conv_dense')
-                or conv.out is not bn_op.z or not conv.layer.trainable or not getattr(self, '_batch_wgrad', False)
+                or conv.out is not bn_op.z or not conv.layer.trainable or not self._bt.batch_wgrad
                 or os.environ.get('DL3P_FOLD_APPLY', '1') == '0' or not self._slab_bytes(conv)):
             return False
         if conv in self._irb_dw or conv in self._irb_expand:
@@ -2038,7 +2040,7 @@ class Executor:
         if conv.kind == 'conv_dense':
             # the direct stem kernel (3 input channels, stride 2) whose input needs no gradient: dl3p_stem_conv_bwd_weight_slabs_bn
             xt = conv.x.tensor
-            return bool(self._stem_direct(conv) and not (xt.requires_grad or xt.root.requires_grad)
+            return bool(self._route(conv) == R_STEM and not (xt.requires_grad or xt.root.requires_grad)
                         and os.environ.get('DL3P_FOLD_APPLY_STEM', '1') != '0')
         M = self.N * conv.Ho * conv.Wo
         if conv.kind == 'conv_dw':
@@ -2078,40 +2080,35 @@ class Executor:
     def _flush_bn_backward(self, P):
         """ONE all-reduce (on the side stream, beside the deferred weight gradients) for every pending BatchNorm, then
         their finalize (global sums -> coefficients) and apply kernels"""
-        pend, self._bwd_pending = self._bwd_pending, []
+        T = self._bt
+        pend, T.pending = T.pending, []
         lo = pend[0][1]
         hi = pend[-1][1] + 2 * pend[-1][0].bn.C
         assert all(b[1] - a[1] == 2 * a[0].bn.C for a, b in zip(pend, pend[1:])), 'backward SyncBatchNorm slices are contiguous'
         L, st = self.L, self.store
-        ctx = P.ctx
-        P.ctx = 'syncbn:' + '+'.join(b.bn.name for b, _, _ in pend)
-        P.coll(lambda t=self.sync_stage[lo:hi]: self.dist.bn_all_reduce_begin(t))
-        self._flush_deferred(P)
-        P.py(self.dist.bn_all_reduce_end)
+        with P.at('syncbn:' + '+'.join(b.bn.name for b, _, _ in pend)):
+            P.coll(lambda t=self.sync_stage[lo:hi]: self.dist.bn_all_reduce_begin(t))
+            self._flush_deferred(P)
+            P.py(self.dist.bn_all_reduce_end)
         for op, off, c in pend:
-            bn = op.bn
-            P.ctx = c
+            bn, z = op.bn, op.z
             aux = self.bn_aux[bn]
             lp = {p.key: p for p in bn.layer.params}
-            z = op.z
             M = self.N * z.H * z.W
-            sp = self.gscale[bn.group.id].data_ptr() + 4 * bn.offset
-            hp = self.gshift[bn.group.id].data_ptr() + 4 * bn.offset
+            sp, hp = self._bn_coeffs(bn)
             mean, invstd, coef = aux['mean'].data_ptr(), aux['invstd'].data_ptr(), aux['coef'].data_ptr()
-            if op in self._irb_bn:
-                # a fused block: the global coefficient triple, then its second pass (which forms dz while it recomputes the expand)
-                self._sync_g.pop(op, None)
+            with P.at(c):
                 P.k(L.bn_bwd_finalize, None, 0, self.sync_stage[off:].data_ptr(), bn.C, float(M * self.dist.world_size),
                     st.ptr(lp['gamma']), invstd, sp, 0, None, None, coef)
-                self._irb_pass_b(P, self._irb_bn[op])
-                continue
-            dzo, lddzo, zp = self.tptr(z, True), z.ld, self.tptr(z)
-            g, ldg = self._sync_g.pop(op, (dzo, lddzo))          # (a residual Add's buffer when the gradient was handed on in place)
-            P.k(L.bn_bwd_finalize, None, 0, self.sync_stage[off:].data_ptr(), bn.C, float(M * self.dist.world_size),
-                st.ptr(lp['gamma']), invstd, sp, 0, None, None, coef)
-            P.k(L.bn_bwd_apply_bf16 if self.bf16 else L.bn_bwd_apply, g, ldg, zp, z.ld, sp, hp, bn.act, mean, invstd, coef,
-                dzo, lddzo, 0, M, bn.C)
-        P.ctx = ctx
+                if op in self._irb_bn:
+                    # a fused block: after the global coefficient triple its second pass (which forms dz while it recomputes the expand)
+                    T.sync_g.pop(op, None)
+                    self._irb_pass_b(P, self._irb_bn[op])
+                    continue
+                dzo, lddzo, zp = self.tptr(z, True), z.ld, self.tptr(z)
+                g, ldg = T.sync_g.pop(op, (dzo, lddzo))          # (a residual Add's buffer when the gradient was handed on in place)
+                P.k(L.bn_bwd_apply_bf16 if self.bf16 else L.bn_bwd_apply, g, ldg, zp, z.ld, sp, hp, bn.act, mean, invstd, coef,
+                    dzo, lddzo, 0, M, bn.C)
 
     # ---------------------------------------------------------------- optimiser
     def _trace_sgd(self):
