@@ -65,10 +65,11 @@ int dl3p_device_cus(void);
  * (pin the wide-tile family), "sb_pipe", "sb_rs" (0 | 1 | -1: the row-stationary form never / wherever it serves / by rule),
  * "conv_sb" (0 | 1 | 2: dense convs on the split kernels never / by the measured rule / wherever supported).  The bf16 path:
  * "bf16_kg" (0 | 1 | 2 | 4: K groups of the tiled GEMM by rule / never / pinned).  A value outside a knob's range restores its
- * default.  Unknown names return DL3P_EINVAL. */
+ * default.  Unknown names return DL3P_EINVAL.  The full list -- every knob's option name, environment variable, default, values and
+ * precedence -- is the table in csrc/options.h (mirrored in INTEGRATION.md, "Options"). */
 int dl3p_set_option(const char* name, int value);
-/* current value of "split_wgrad" | "conv_sb" | "sb_rs" | "sb_pipe" (the knobs that decide how many slabs / partial rows a launch
- * writes: a host that records launches pins them again before replaying them); INT_MIN for any other name */
+/* current value of "split_wgrad" | "conv_sb" | "sb_rs" | "sb3" | "sb_pipe" | "splitk" (the knobs that decide how many slabs / partial
+ * rows a launch writes: a host that records launches pins them again before replaying them); INT_MIN for any other name */
 int dl3p_get_option(const char* name);
 /* What the dispatcher WOULD launch for a pointwise GEMM / a depthwise conv, without launching it (the parity tests over
  * the measured tables use it to prove that a table row is reached and what it selects).
@@ -76,7 +77,12 @@ int dl3p_get_option(const char* name);
  * gradient + fused BatchNorm sums, 4 weight gradient; (M, K, N) = rows, reduction length, output columns of the GEMM as
  * launched (data gradient: K = the conv's output channels).  out6 = {kernel family (0 tiled MFMA, 1 wave-streaming, 2 few-row),
  * nt (role 4: tile index), tile rows / 64 (role 4: workgroups per CU), grid x (role 4: tiles), grid y (role 4: M splits), 1 if
- * the row came from csrc/gemm_tuned.h}.
+ * the row came from csrc/gemm_tuned.h}.  Roles 5..8: the split-bf16 twin of role - 5, out6 = {3, nt, mi, kernel form (0 producer /
+ * consumer, 1 tiled, 2 wide, 3 row-stationary, 4 pinned-schedule), workgroups, from csrc/sb_tuned.h} or {-1} where the tiled kernels
+ * do not serve the shape; role 9: the split-bf16 weight gradient.  The query runs the planners the entry points run, but it knows
+ * the shape only: it reports the SHAPE-LEVEL route.  A launch whose input activation, bias, pitch or leading dimension the
+ * pinned-schedule form does not serve (dl3p_pwconv_fwd_sb refuses the form inside its plan) takes the form the query reports
+ * with "sb3" = 0; likewise the streaming / few-row kernels where an entry point's epilogue rules them out.
  * dl3p_dw_plan_query: role 0 forward, 1 data gradient, 2 data gradient + fused BatchNorm sums, 3 weight gradient, with the
  * conv's OWN geometry (as the entry points take it).  out6 = {kind (0 gather, 1 window stride 1, 2 window stride 2, 3 residue
  * lattice, 4 quad / strided data gradient), strip width, band height, bands, workgroups per slab, 1 if from csrc/dw_tuned.h}. */

@@ -612,6 +612,46 @@ def test_pinned_schedule_forward_is_the_default_on_the_long_decoder_layers_only(
         L.set_option(b'pw_small_min_rows', 64)
 
 
+def test_a_launch_the_pinned_schedule_form_does_not_serve_takes_the_tiled_plan(ops):
+    """sb3 = 1 pins the pinned-schedule form wherever the SHAPE is served (the plan query reports it); the planner refuses it for a
+    launch whose input activation it has no instantiation for (hard-swish) or that wants statistics and a bias together, and
+    plans such a launch as if sb3 were 0.  Both runs then take the same tiled kernel, which is deterministic: output,
+    statistic partials and their row count are bit-identical, no tolerance"""
+    M, K, N = 300, 256, 256
+    L = ops.lib()
+    g = torch.Generator(device=DEV); g.manual_seed(31)
+    rnd = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    x, wt = rnd(M, K), rnd(N, K) / K ** 0.5
+    sc, sh, bias = torch.rand(K, device=DEV, generator=g) + 0.5, rnd(K) * 0.3 + 0.2, rnd(N) * 0.1
+    wsp = ops.split_bf16x3(wt)
+    launches = {'hswish': (None, ops.ACT_HSWISH, False), 'stats_and_bias': (bias, ops.ACT_RELU, True)}
+
+    def run(sb3):
+        L.set_option(b'sb3', sb3)
+        out = {}
+        for name, (b, act, stats) in launches.items():
+            part = torch.zeros(ops.MAX_STAT_ROWS * 2 * N, device=DEV) if stats else None
+            res = ops.pwconv_fwd_sb(x, wsp, K, b, sc, sh, act, partials=part)
+            out[name] = (res[0], res[1], part) if stats else (res, None, None)
+        torch.cuda.synchronize()
+        return out
+    L.set_option(b'pw_small_min_rows', -1)
+    try:
+        L.set_option(b'sb3', 1)
+        assert _plan(L, 5, M, K, N)[3] == 4 and _plan(L, 6, M, K, N)[3] == 4       # the shape-level route: pinned
+        pinned, tiled = run(1), run(0)
+        assert _plan(L, 5, M, K, N)[3] != 4
+        for name in launches:
+            (y1, rows1, p1), (y0, rows0, p0) = pinned[name], tiled[name]
+            assert torch.equal(y1, y0), name
+            assert rows1 == rows0, (name, rows1, rows0)
+            if p1 is not None:
+                assert rows1 > 0 and torch.equal(p1, p0), name
+    finally:
+        L.set_option(b'pw_small_min_rows', 64)
+        L.set_option(b'sb3', -1)
+
+
 @pytest.mark.parametrize('act_name,front_act', [('relu', 'relu'), ('relu6', 'relu6'), ('none', 'relu')])
 @pytest.mark.parametrize('M', [16 * 129 * 129, 70001, 300])
 def test_pinned_schedule_data_gradient_with_the_folded_apply(ops, M, act_name, front_act):

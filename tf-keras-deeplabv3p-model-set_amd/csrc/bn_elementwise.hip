@@ -335,7 +335,7 @@ extern "C" int dl3p_reduce_rows_batched(const void* jobs, const int* blockmap0, 
   DL3P_CHECK_ARG(jobs && blocks0 >= 0 && blocks1 >= 0 && (!blocks0 || blockmap0) && (!blocks1 || blockmap1),
                  "dl3p_reduce_rows_batched: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  static const int per_cu = getenv("DL3P_RB_PER_CU") ? atoi(getenv("DL3P_RB_PER_CU")) : 8;      // (0: one workgroup per block)
+  static const int per_cu = env_int("DL3P_RB_PER_CU", 8);      // (0: one workgroup per block)
   if (blocks0)
     hipLaunchKernelGGL(reduce_rows_batched_wide_kernel, dim3(per_cu > 0 ? std::min(blocks0, per_cu * dl3p_device_cus()) : blocks0),
                        dim3(256), 0, st, (const ReduceJob*)jobs, (const int2*)blockmap0, blocks0);
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(EwParams p) {
 static int ew_setup(EwParams& p, long long M, int C, int max_rows) {
   pick_lanes(C, &p.c4s, &p.px, &p.nslab);
   long long need = ceil_div_ll(M, p.px);
-  static const int ew_per_cu = getenv("DL3P_EW_PER_CU") ? atoi(getenv("DL3P_EW_PER_CU")) : 4;   // 8 -> 4: fewer partial rows for the finalize kernels, same streaming rate
+  static const int ew_per_cu = env_int("DL3P_EW_PER_CU", 4);   // 8 -> 4: fewer partial rows for the finalize kernels, same streaming rate
   long long target = DL3P_NUM_CUS * ew_per_cu / p.nslab;
   if (target < 1) target = 1;
   long long nbx = need < target ? need : target;
@@ -853,7 +853,7 @@ static PoolPlan pool_plan(int N, int HW, int C, bool chunked) {
   pl.c4s = d; pl.px = 256 / d; pl.nslab = c4 / d;
   int nchunk = 1;
   if (chunked) {
-    static const int want = getenv("DL3P_POOL_WGS") ? atoi(getenv("DL3P_POOL_WGS")) : 512;
+    static const int want = env_int("DL3P_POOL_WGS", 512);
     nchunk = (want + N * pl.nslab - 1) / (N * pl.nslab);
     const int most = (HW + 4 * pl.px - 1) / (4 * pl.px);          // >= 4 pixels per lane and chunk
     if (nchunk > most) nchunk = most;

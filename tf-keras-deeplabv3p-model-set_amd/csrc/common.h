@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "../../include/dl3p.h"
 
 #define DL3P_NUM_CUS 256
@@ -32,6 +33,12 @@ void dl3p_set_error(const char* fmt, ...);
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+// an integer environment variable, `d` when it is absent.  Callers keep the value in a function-local static (or in the
+// option table, options.h), so each variable is read once, on first use
+static inline int env_int(const char* name, int d) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : d;
+}
 
 // ---------------------------------------------------------------------------------- device
 // Activations are evaluated BRANCH-FREE from wave-uniform constants derived from the activation code:
@@ -164,9 +171,6 @@ void dl3p_pw_tiny_nt(const float* a, int lda, const float* scale, const float* s
                      hipStream_t st);
 void dl3p_pw_tiny_wgrad(const float* x, int ldx, const float* scale, const float* shift, int act, const float* dy,
                         int lddy, float* gw, float* gb, int M, int K, int N, hipStream_t st);
-
-// depthwise plan knobs moved by dl3p_set_option (defined in dwconv.hip): 0 = automatic
-extern int dl3p_dw_force_per_cu, dl3p_dw_force_want, dl3p_dw_force_maxth, dl3p_dw_force_tw, dl3p_dw_use_table;
 
 int dl3p_reduce_rows_impl(const float* partials, int rows, size_t n, float* out, int accumulate, hipStream_t st);
 int dl3p_reduce_rows_strided_impl(const float* partials, int rows, size_t row_stride, size_t n, float* out,

@@ -13,6 +13,7 @@
 // The BN+activation of the producing layer is applied on load (prologue): zero padding is in
 // activation space, so out-of-range taps contribute exactly 0.
 #include "bf16.h"
+#include "options.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1309,9 +1310,8 @@ static int check_dw_common(const char* fn, const void* x, int ldx, int C, int k)
 // rows per band: as tall as possible (less halo re-reading: at th = 1 every input row is fetched 3x from L2 and the
 // 33x33 layers were L2-bound) while every CU still gets 1-2 workgroup-iterations (measured optimum 256-512)
 static int pick_band(long long items_per_row_band, int rows, int px, int nslab) {
-  static const int want_env = getenv("DL3P_DW_WANT") ? atoi(getenv("DL3P_DW_WANT")) : DL3P_NUM_CUS * 3 / 2;
-  const long long want = want_env;                               // workgroup-iterations wanted overall
-  static const int force = getenv("DL3P_DW_BAND") ? atoi(getenv("DL3P_DW_BAND")) : 0;
+  const long long want = opt_env(OPT_DW_WANT);                             // workgroup-iterations wanted overall
+  static const int force = env_int("DL3P_DW_BAND", 0);
   if (force && rows <= 40) return force;
   int th = 16;
   while (th > 1 && (items_per_row_band * ceil_div(rows, th) / px) * nslab < want) th >>= 1;
@@ -1326,7 +1326,7 @@ static int pick_band(long long items_per_row_band, int rows, int px, int nslab) 
 // sub-lattices of rate 2: 37 vs 55 us at 33x33x672), 2 on the wide ones (65x65x120: 49 vs 58 us, the bands stay taller).
 // DL3P_DW5_ROWS = 2 | 4 forces one, 0 selects the older register-window kernel (1 wave per SIMD, kept for comparison).
 static int dw5_rows_tw(int uw) {
-  static const int v = getenv("DL3P_DW5_ROWS") ? atoi(getenv("DL3P_DW5_ROWS")) : -1;
+  static const int v = env_int("DL3P_DW5_ROWS", -1);
   if (v >= 0) return v;
   return uw <= 40 ? 4 : 2;
 }
@@ -1338,10 +1338,8 @@ static int dw5_tw(int uw) { return dw5_rows_tw(uw) == 4 ? 4 : 2; }
 // workgroups per CU; want: workgroup-iterations the row-band split aims for; maxth: tallest band.  0 = keep the default.
 struct DwTuned { int role, N, H, W, C, k, stride, rate, per_cu, want, maxth, tw; };   // tw: strip width of the 3x3 stride-1 window kernels (0 / 4, or 2)
 #include "dw_tuned.h"
-int dl3p_dw_force_per_cu = 0, dl3p_dw_force_want = 0, dl3p_dw_force_maxth = 0, dl3p_dw_force_tw = 0, dl3p_dw_use_table = -1;
 static const DwTuned* dw_tuned_lookup(const DwParams& p) {
-  if (dl3p_dw_use_table < 0) dl3p_dw_use_table = getenv("DL3P_DW_TUNED") ? atoi(getenv("DL3P_DW_TUNED")) : 1;
-  if (!dl3p_dw_use_table) return nullptr;
+  if (!opt(OPT_DW_TUNED)) return nullptr;
   const int role = p.bb_z ? 2 : (p.flip ? 1 : (p.dy ? 3 : 0));
   for (size_t i = 0; i < sizeof(g_dw_tuned) / sizeof(g_dw_tuned[0]); ++i) {
     const DwTuned& e = g_dw_tuned[i];
@@ -1359,10 +1357,10 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
     if (e->per_cu) per_cu = e->per_cu;
     t_want = e->want; t_maxth = e->maxth; t_tw = e->tw;
   }
-  if (dl3p_dw_force_tw) t_tw = dl3p_dw_force_tw;
-  if (dl3p_dw_force_per_cu) per_cu = dl3p_dw_force_per_cu;
-  if (dl3p_dw_force_want) t_want = dl3p_dw_force_want;
-  if (dl3p_dw_force_maxth) t_maxth = dl3p_dw_force_maxth;
+  if (opt_set(OPT_DW_TW)) t_tw = opt_set(OPT_DW_TW);
+  if (opt_set(OPT_DW_PER_CU)) per_cu = opt_set(OPT_DW_PER_CU);
+  if (opt_set(OPT_DW_WANT)) t_want = opt_set(OPT_DW_WANT);
+  if (opt_set(OPT_DW_MAXTH)) t_maxth = opt_set(OPT_DW_MAXTH);
   // 5x5: window kernels with LDS weights in the forward / data-gradient role (strips of 2 at stride 1, 1 at stride 2);
   // the weight gradient keeps the per-pixel gather (25 tap accumulators + a 5-row window do not fit)
   if (p.ks5 && !window5) kind = 0;
@@ -1372,7 +1370,7 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
       2 * p.rate >= p.H && 2 * p.rate >= p.W && p.rate < p.H && p.rate < p.W &&
       (long long)p.N * p.H * p.W * (p.ldx > p.ldy ? p.ldx : p.ldy) < (1LL << 31)) { kind = 3; p.lat = 2; }
   // one step down: 3 * rate covers the map (rate 12 on 33 x 33, rate 36 on 97 x 97) -> 3 x 3 pixels per class
-  static const int lat3 = getenv("DL3P_DW_LAT3") ? atoi(getenv("DL3P_DW_LAT3")) : 1;
+  static const int lat3 = env_int("DL3P_DW_LAT3", 1);
   if (kind == 0 && lat3 && p.ks == 3 && p.stride == 1 && p.pad_t == p.rate && p.pad_l == p.rate && p.Ho == p.H && p.Wo == p.W &&
       3 * p.rate >= p.H && 3 * p.rate >= p.W && p.rate < p.H && p.rate < p.W &&
       (long long)p.N * p.H * p.W * (p.ldx > p.ldy ? p.ldx : p.ldy) < (1LL << 31)) { kind = 3; p.lat = 3; }
@@ -1391,12 +1389,10 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
     p.tw = TW;
     p.spr = ceil_div(uw, TW);
     // bands of equal height (+-1 row) instead of full ones and a remainder: 33 rows as 11+11+11, not 16+16+1
-    static const int balance = getenv("DL3P_DW_BALANCE") ? atoi(getenv("DL3P_DW_BALANCE")) : 2;
+    static const int balance = env_int("DL3P_DW_BALANCE", 2);
     if (balance == 2) {
       // the fewest bands (tallest, least halo re-reading) that still give every CU its workgroup-iterations
-      static const int want_env = getenv("DL3P_DW_WANT") ? atoi(getenv("DL3P_DW_WANT")) : DL3P_NUM_CUS * 3 / 2;
-      static const int maxth_env = getenv("DL3P_DW_MAXTH") ? atoi(getenv("DL3P_DW_MAXTH")) : 16;
-      const int want = t_want ? t_want : want_env, maxth = t_maxth ? t_maxth : maxth_env;
+      const int want = t_want ? t_want : opt_env(OPT_DW_WANT), maxth = t_maxth ? t_maxth : opt_env(OPT_DW_MAXTH);
       const long long per_band = (long long)p.N * r * r * p.spr;
       int nb = ceil_div(uh, maxth);
       while (nb < uh && (per_band * nb / p.px) * p.nslab < want) ++nb;
@@ -1411,8 +1407,8 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
     }
     p.total = (long long)p.N * r * r * p.nbands * p.spr;
   }
-  static const int lat2_per_cu = getenv("DL3P_LAT2_PER_CU") ? atoi(getenv("DL3P_LAT2_PER_CU")) : DL3P_LAT2_PER_CU;
-  static const int lat3_per_cu = getenv("DL3P_LAT3_PER_CU") ? atoi(getenv("DL3P_LAT3_PER_CU")) : 3;
+  static const int lat2_per_cu = env_int("DL3P_LAT2_PER_CU", DL3P_LAT2_PER_CU);
+  static const int lat3_per_cu = env_int("DL3P_LAT3_PER_CU", 3);
   p.nbx = pick_nbx(p.total, p.px, p.nslab, kind == 3 ? (p.lat == 3 ? lat3_per_cu : lat2_per_cu) : per_cu);
   return kind;
 }
@@ -1466,7 +1462,7 @@ static void launch_fwd_pro(const DwParams& p, int kind, dim3 grid, hipStream_t s
 static int plan_forward(DwParams& p, int KS, int tw5) {
   p.ks = KS;
   p.ks5 = KS == 5;
-  static const int dwf_per_cu = getenv("DL3P_DWF_PER_CU") ? atoi(getenv("DL3P_DWF_PER_CU")) : 8;
+  static const int dwf_per_cu = env_int("DL3P_DWF_PER_CU", 8);
   if (KS == 5) {          // keep the LDS weight tile small: at most 64 channel lanes per workgroup
     const int c4 = p.C / 4;
     int best = 1;
@@ -1483,13 +1479,13 @@ static void launch_fwd(const DwParams& p0, hipStream_t st) {
   const int kind = plan_forward(p, KS, 0);
   // streaming stores for forward outputs (bit 0 window kernels, bit 1 gather): -0.09 ms per step, and the rate-18
   // lattice kernel (always streaming) keeps its input in L2: 9.6 -> 8.8 us in-step
-  static const int nt_mask = getenv("DL3P_DW_NT") ? atoi(getenv("DL3P_DW_NT")) : 3;
+  static const int nt_mask = env_int("DL3P_DW_NT", 3);
   p.nt = (p.flip == 0 && !p.accumulate) ? ((kind == 0 ? (nt_mask >> 1) : nt_mask) & 1) : 0;
   // counted-wait rows (dw_fwd_seg FAST): measured on MI355X they pay where the row's stores are slow to retire -- the STREAMING stores
   // of forward launches on tensors far beyond the caches (decoder_conv0 / conv1_depthwise at batch 16: 142.9 -> 137.5, 127.4 -> 108.0 us)
   // -- and lose 10-15 % on cache-sized tensors and on every data gradient (plain stores retire at L2 anyway).  DL3P_DW_FAST_ROWS:
   // 0 never, 1 that rule (default), 2 every launch that can
-  static const int fast_rows = getenv("DL3P_DW_FAST_ROWS") ? atoi(getenv("DL3P_DW_FAST_ROWS")) : 1;
+  static const int fast_rows = env_int("DL3P_DW_FAST_ROWS", 1);
   const long long out_bytes = (long long)p.N * p.Ho * p.Wo * p.C * 4;
   p.fast_rows = fast_rows >= 2 || (fast_rows == 1 && p.nt && out_bytes >= (200ll << 20));
   dim3 grid(p.nbx * p.nslab);
@@ -1732,9 +1728,9 @@ static int dwconv2d_bwd_weight_impl(const float* x, int ldx, const float* in_sca
   p.pad_t = pad_t; p.pad_l = pad_l;
   pick_lanes(C, &p.c4s, &p.px, &p.nslab);
   p.ks5 = k == 5;
-  static const int dww_per_cu = getenv("DL3P_DWW_PER_CU") ? atoi(getenv("DL3P_DWW_PER_CU")) : 2;   // fewer slabs: the slab reduce costs as much as the kernel at 8
+  static const int dww_per_cu = env_int("DL3P_DWW_PER_CU", 2);   // fewer slabs: the slab reduce costs as much as the kernel at 8
   // 5x5 stride 1: rolling-row kernel with strips of DL3P_DW5_WROWS (1 | 2) columns, 0 = per-pixel gather
-  static const int wrows = getenv("DL3P_DW5_WROWS") ? atoi(getenv("DL3P_DW5_WROWS")) : 2;
+  static const int wrows = env_int("DL3P_DW5_WROWS", 2);
   const bool rows5 = k == 5 && stride == 1 && wrows > 0;
   const int kind = fwd_plan(p, dww_per_cu, rows5, wrows);
   if (kind_out) { *kind_out = kind; return DL3P_OK; }      // plan query (dl3p_dwconv2d_bwd_weight_bn_supported)
@@ -1830,7 +1826,7 @@ extern "C" int dl3p_dwconv2d_bwd_weight_slabs(const float* x, int ldx, const flo
 int dl3p_dw_window_bf16(int role, const void* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const void* w,
                         void* y, int ldy, float* partials, int* rows_out, int accumulate, int N, int H, int W, int C, int k,
                         int stride, int rate, int pad_t, int pad_l, int Ho, int Wo, hipStream_t st) {
-  static const int on = getenv("DL3P_BF16_DW_WINDOW") ? atoi(getenv("DL3P_BF16_DW_WINDOW")) : 1;
+  static const int on = env_int("DL3P_BF16_DW_WINDOW", 1);
   if (!on || C <= 0 || C % 4 || (k != 3 && k != 5) || ldx % 4 || ldy % 4 || ((uintptr_t)x & 7u) || ((uintptr_t)y & 7u) || ((uintptr_t)w & 7u))
     return 0;
   if (role == 1 && stride != 1) return 0;
@@ -1876,7 +1872,7 @@ int dl3p_dw_window_bf16(int role, const void* x, int ldx, const float* in_scale,
 int dl3p_dw_window_wgrad_bf16(const void* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const void* dy,
                               int lddy, float* workspace, int max_rows, int* rows_out, int N, int H, int W, int C, int k,
                               int stride, int rate, int pad_t, int pad_l, int Ho, int Wo, hipStream_t st) {
-  static const int on = getenv("DL3P_BF16_DW_WINDOW") ? atoi(getenv("DL3P_BF16_DW_WINDOW")) : 1;
+  static const int on = env_int("DL3P_BF16_DW_WINDOW", 1);
   if (!on || k != 3 || C <= 0 || C % 4 || ldx % 4 || lddy % 4 || ((uintptr_t)x & 7u) || ((uintptr_t)dy & 7u) || max_rows < DL3P_NUM_XCDS) return 0;
   // few pixels (Xception's 33 x 33 maps at batch 4: 4356): the strip kernel's finer work items fill the chip better -- 27.4 against
   // 34.2 us on 33 x 33 x 728; from 65 x 65 x 4 up the window kernel ties or wins (129 x 129 x 256 stride 2: 35.5 against 49.5)
@@ -1937,8 +1933,8 @@ extern "C" int dl3p_dw_plan_query(int role, int N, int H, int W, int C, int k, i
     p.x = dummy; p.ldx = C; p.dy = dummy; p.lddy = C;
     p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
     p.ks5 = k == 5;
-    static const int dww_per_cu = getenv("DL3P_DWW_PER_CU") ? atoi(getenv("DL3P_DWW_PER_CU")) : 2;
-    static const int wrows = getenv("DL3P_DW5_WROWS") ? atoi(getenv("DL3P_DW5_WROWS")) : 2;
+    static const int dww_per_cu = env_int("DL3P_DWW_PER_CU", 2);
+    static const int wrows = env_int("DL3P_DW5_WROWS", 2);
     kind = fwd_plan(p, dww_per_cu, k == 5 && stride == 1 && wrows > 0, wrows);
   }
   out6[0] = kind; out6[1] = p.tw; out6[2] = p.th; out6[3] = p.nbands; out6[4] = p.nbx; out6[5] = dw_tuned_lookup(p) != nullptr;

@@ -15,11 +15,11 @@
 // pixel (one 8-byte store per accumulator).  The weight gradient needs both operands transposed (the reduction runs
 // over rows): tiles are staged row-major and read back with ds_read_b64_tr_b16, the hardware transpose read.
 #include "bf16.h"
+#include "options.h"
 #include <string.h>
 #include <stdlib.h>
 #include <type_traits>
 
-int dl3p_bf16_force_kg = -1;      // dl3p_set_option("bf16_kg", 0 | 1 | 2 | 4 | -1): K groups of pwb_gemm by rule / never / pinned / default (DL3P_BF16_KG)
 
 namespace {
 
@@ -818,10 +818,10 @@ int gemm_b(const char* fn, GemmB p, bool a_f32, bool y_f32, int* rows_out, hipSt
     DL3P_CHECK_LAUNCH(fn);
     return DL3P_OK;
   }
-  static const int dbg = getenv("DL3P_BF16_DBG") ? atoi(getenv("DL3P_BF16_DBG")) : 0;
+  static const int dbg = env_int("DL3P_BF16_DBG", 0);
   p.dbg = dbg;
   const bool stats = p.partials != nullptr;
-  static const int no_stream = getenv("DL3P_BF16_NOSTREAM") ? atoi(getenv("DL3P_BF16_NOSTREAM")) : 0;
+  static const int no_stream = env_int("DL3P_BF16_NOSTREAM", 0);
   const StreamPlan sp = stream_plan_b(p.K, p.N, stats);
   // (the streaming kernel pays a [BN][K] weight load per workgroup and runs one workgroup of 8 waves per CU: it wins from
   // ~2^16 rows up -- 131072 x 304 -> 256: 67 us against 91 us tiled -- and loses on the 128 x 256 and 64 x 128 maps)
@@ -846,12 +846,11 @@ int gemm_b(const char* fn, GemmB p, bool a_f32, bool y_f32, int* rows_out, hipSt
   int gy = ceil_div(p.N, 16 * nt);
   // 64-row tiles whenever 128-row tiles would leave the chip under two workgroups per CU (the 64 x 128 maps: M = 8192)
   int mi = (nt == 16 || (long long)ceil_div(p.M, 128) * gy < 2LL * DL3P_NUM_CUS) ? 1 : 2;
-  static const int force_mi = getenv("DL3P_BF16_MI") ? atoi(getenv("DL3P_BF16_MI")) : 0;     // A/B knob
+  static const int force_mi = env_int("DL3P_BF16_MI", 0);     // A/B knob
   if (force_mi && nt != 16) mi = force_mi;
   // few row tiles and a long reduction: K groups inside the workgroup (pwb_gemm, KG > 1)
-  static const int env_kg = getenv("DL3P_BF16_KG") ? atoi(getenv("DL3P_BF16_KG")) : 0;       // 0: the rule; 1: never; 2 / 4: wherever possible
-  const int force_kg = dl3p_bf16_force_kg >= 0 ? dl3p_bf16_force_kg : env_kg;                 // dl3p_set_option("bf16_kg", ...) first
-  static const int force_kg_nt = getenv("DL3P_BF16_KG_NT") ? atoi(getenv("DL3P_BF16_KG_NT")) : 0;
+  const int force_kg = opt(OPT_BF16_KG);       // 0: the rule; 1: never; 2 / 4: wherever possible
+  static const int force_kg_nt = env_int("DL3P_BF16_KG_NT", 0);
   int kgroups = 1;
   if (force_kg != 1 && !a_f32 && !y_f32 && p.N >= 32) {       // (with or without the backward sums: the two data gradients stay bit-identical)
     const int nk = ceil_div(p.K, BK);

@@ -41,3 +41,27 @@ struct GemmParams {
   const float* f_z; int f_ldz; const float* f_scale; const float* f_shift; const float* f_mean; const float* f_invstd;
   const float* f_coef; int f_act; float* f_dz; int f_lddz;
 };
+
+// ---- host functions of the other GEMM translation units that pwconv.hip plans for and launches
+// pw_split.hip: the tiled / wide forms (wm > 1 or nt > 8 selects the wide-tile family), the producer / consumer form, the
+// split weight gradient
+void dl3p_launch_gemm_sb(const GemmParams& p, bool stats, bool bnb, bool ga, int nt, int mi, int wm, dim3 grid, hipStream_t st);
+void dl3p_launch_gemm_sbp(const GemmParams& p, bool stats, bool bnb, int nt, int mi, dim3 grid, hipStream_t st);
+bool dl3p_sb_wide_config(int nt, int mi, int wm);
+int dl3p_wgrad_sb_plan(int M, int K, int N, int max_slabs, int tile, int per_cu, int* kf, int* nw, int* ktiles, int* ntiles, int* mrows);
+void dl3p_launch_wgrad_sb(const float* x, int ldx, const float* scale, const float* shift, int act, const float* dy, int lddy,
+                          float* slabs, int M, int K, int N, int kf, int nw, int ktiles, int ntiles, int mrows, int splits, hipStream_t st);
+void dl3p_launch_wgrad_sb_gx(const float* x, int ldx, const float* scale, const float* shift, int act, const float* dy, int lddy,
+                             float* slabs, int M, int K, int N, const int* geo, int kf, int nw, int ktiles, int ntiles, int mrows, int splits,
+                             hipStream_t st);
+// pw_split_rs.hip: the row-stationary form (mode 0 plain, 1 forward statistics, 2 fused BatchNorm-backward sums)
+bool dl3p_sb_rs_supported(int role, int M, int K, int N);
+bool dl3p_sb_rs_fold_supported(int M, int K, int N, int act);
+int dl3p_sb_rs_grid(int M);
+bool dl3p_launch_gemm_sbr(const GemmParams& p, int mode, int grid, hipStream_t st);
+// pw_split3.hip: the pinned-schedule form, forward and data gradient with the folded BatchNorm-backward apply
+bool dl3p_sb3_supported(int role, int M, int K, int N, int pitch, int act, bool has_scale, bool accumulate, bool bias, int ld_max);
+bool dl3p_sb3d_supported(int M, int kout, int nred, int pitch, int f_act, int bb_act, bool bnb, bool accumulate, int ld_max);
+int dl3p_sb3_grid(int M);
+bool dl3p_launch_gemm_sb3(GemmParams p, bool stats, int grid, hipStream_t st);
+bool dl3p_launch_gemm_sb3d(GemmParams p, bool bnb, int grid, hipStream_t st);

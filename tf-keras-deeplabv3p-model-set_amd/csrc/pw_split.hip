@@ -1132,7 +1132,7 @@ void dl3p_launch_wgrad_sb(const float* x, int ldx, const float* scale, const flo
     // SLOWER in the step (12.83 against 12.76 ms, same box): the second launch streams dY from HBM once more, where the six tiles
     // of a slice in ONE launch share it through L2.  Opt-in (DL3P_WGRAD_SB_MIXED=1), parity-tested, not the default.
     const int rem = K % 128;
-    static const int mixed = getenv("DL3P_WGRAD_SB_MIXED") ? atoi(getenv("DL3P_WGRAD_SB_MIXED")) : 0;
+    static const int mixed = env_int("DL3P_WGRAD_SB_MIXED", 0);
     if (mixed && rem > 0 && rem <= 64 && ktiles > 1) {
       p.ktiles = ktiles - 1;
       launch_wgrad_tile<2, 8, 2, false>(p, dim3(p.ktiles * ntiles, splits), st);

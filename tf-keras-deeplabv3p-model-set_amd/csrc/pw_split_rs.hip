@@ -520,13 +520,13 @@ static bool launch_sbr_nk(const GemmParams& p, int grid, hipStream_t st) {
   } else if (nk == 8) {
     // K = 256: four chunks per staging slot (244 / 288 / 218 us forward / data gradient + sums / plain on 266256 rows against 255 / 311 /
     // 233 with two); K = 320: two -- five spill (335 against 372 us)
-    static const int cps = getenv("DL3P_SB_RS_CPS") ? atoi(getenv("DL3P_SB_RS_CPS")) : 4;
+    static const int cps = env_int("DL3P_SB_RS_CPS", 4);
     if (cps == 4) launch_sbr_one<8, 32, MODE, 4>(p, grid, st);
     else launch_sbr_one<8, 32, MODE, 2>(p, grid, st);
   }
   else if (nk == 10) {
     if constexpr (MODE != 2) {      // (K = 320 leaves no room for the second statistics patch)
-      static const int cg16 = getenv("DL3P_SB_RS_CG16") ? atoi(getenv("DL3P_SB_RS_CG16")) : 0;
+      static const int cg16 = env_int("DL3P_SB_RS_CG16", 0);
       if (cg16) launch_sbr_one<10, 16, MODE>(p, grid, st);
       else launch_sbr_one<10, 32, MODE>(p, grid, st);
     } else return false;

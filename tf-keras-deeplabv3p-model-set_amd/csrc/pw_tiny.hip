@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void pw_tiny_wgrad_kernel(TinyWgradParams p) {
 }
 
 int tiny_max_rows() {
-  static const int v = getenv("DL3P_PW_TINY_ROWS") ? atoi(getenv("DL3P_PW_TINY_ROWS")) : 64;
+  static const int v = env_int("DL3P_PW_TINY_ROWS", 64);
   return v;
 }
 

@@ -267,7 +267,7 @@ extern "C" int dl3p_resize_bilinear_fwd(const float* x, int ldx, float* y, int l
   ResizeParams p = {};
   p.x = x; p.ldx = ldx; p.y = y; p.ldy = ldy; p.N = N; p.h = h; p.w = w; p.C = C; p.H = H; p.W = W;
   pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  static const int strip_ok = getenv("DL3P_RESIZE_STRIP") ? atoi(getenv("DL3P_RESIZE_STRIP")) : 1;      // (A/B switch)
+  static const int strip_ok = env_int("DL3P_RESIZE_STRIP", 1);      // (A/B switch)
   if (strip_ok && W >= 2 * w && C % 256 == 0) {
     // SEG outputs lie between at most RS_NCOL = 6 input columns: floor((SEG - 1) w / W) + 3 <= 6
     const int seg = (15ll * w) / W <= 3 ? 16 : 8;
@@ -296,7 +296,7 @@ extern "C" int dl3p_resize_bilinear_bwd(const float* gy, int ldgy, float* gx, in
   ResizeParams p = {};
   p.x = gy; p.ldx = ldgy; p.y = gx; p.ldy = ldgx; p.N = N; p.h = h; p.w = w; p.C = C; p.H = H; p.W = W;
   p.accumulate = accumulate;
-  static const int tight = getenv("DL3P_RESIZE_TIGHT") ? atoi(getenv("DL3P_RESIZE_TIGHT")) : 1;      // (A/B switch)
+  static const int tight = env_int("DL3P_RESIZE_TIGHT", 1);      // (A/B switch)
   p.tight = tight;
   pick_lanes(C, &p.c4s, &p.px, &p.nslab);
   p.total = (long long)N * h * w;

@@ -319,11 +319,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(StemParams p) {
 }
 
 static int stem_grid(int tiles, int per_cu) {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = getenv("DL3P_STEM_PER_CU");
-    env = e ? atoi(e) : 0;
-  }
+  static const int env = env_int("DL3P_STEM_PER_CU", 0);
   if (env > 0) per_cu = env;
   long long want = (long long)DL3P_NUM_CUS * per_cu;
   long long need = ceil_div_ll(ceil_div_ll(tiles, DL3P_NUM_XCDS), 4) * DL3P_NUM_XCDS;
