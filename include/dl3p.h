@@ -669,6 +669,38 @@ int dl3p_rmsprop_step_avg(float* w, float* v, const float* g, size_t n, const fl
 int dl3p_weight_average(float* w, float* avg, size_t n, int avg_mode, float avg_coef, int avg_period, int avg_start,
                         const int64_t* step_counter, const float* lr_scale_elem, void* stream);
 
+/* Gradient clipping (csrc/grad_clip.hip): clipvalue, clipnorm, global_clipnorm of the Keras optimisers (common/model_utils.py:117-123)
+ * on the flat gradient buffer, in front of an optimiser entry point above.  What is clipped is the gradient of the whole loss,
+ * g' = fmaf(g, grad_scale, 2 * l2_elem * w) (float32, the value the optimiser kernels form); elements with lr_scale_elem == 0 enter no
+ * norm and keep their g.  Order: value clamp (clip_value > 0; NaN stays NaN), then ONE of the two norm rules:
+ *   mode 1, per variable:  s_v = threshold / max(|g'_v|, threshold)        mode 2, global:  s = threshold / max(|g'|, threshold)
+ * Sums of squares, norms, the comparison and the quotient are float64, the quotient is rounded once to float32: exactly 1.0f at or
+ * below the threshold (also for an all-zero or wholly frozen variable), NaN for a NaN norm, 0 for an infinite per-variable norm (whose
+ * infinite elements then come out NaN, nothing else is touched), NaN for EVERY variable when the global norm is not finite (as
+ * tf.clip_by_global_norm).  Fixed summation order, no atomics: bitwise repeatable.
+ *   tables   vars[nvars][3] = {offset, length, first block}: a variable is `length` floats at `offset` of the flat buffers, both
+ *            multiples of 4 (16-byte boundaries; pad with frozen elements), its blocks are first block .. first block + ceil(length /
+ *            dl3p_grad_clip_block_elements()) - 1, numbered through the variables in order; blockmap[nblocks][2] = {variable, block
+ *            within the variable}, one workgroup each.  `vars` / `blockmap` are device arrays, `*_host` the same tables in host memory:
+ *            the calls check them (every block inside its variable, every variable inside the n floats, nvars <= 65536) together with
+ *            null / misaligned pointers and return DL3P_EINVAL before any launch.
+ *   sumsq    partials[b] = sum over the trainable elements of block b of clamp(g')^2                      (reads g, w, l2_elem, mask)
+ *   finalize norm[v] = sqrt(sum of the partials of variable v), norm[nvars] = the global norm, scale[v] by `mode`   (one workgroup)
+ *   apply    g <- clamp(g') * scale[variable] in place for every trainable element (scale NULL: the clamp alone, clip_value > 0); the
+ *            optimiser call behind it then takes grad_scale = 1 and l2_elem = NULL.  partials non-NULL: also leaves sumsq's partials
+ *            of the clamped, unscaled gradient (their sum over b, square-rooted, is the global norm).
+ * w may be NULL with l2_elem NULL; lr_scale_elem NULL = everything trainable.  Asynchronous on `stream`, no allocation. */
+int dl3p_grad_clip_block_elements(void);
+int dl3p_grad_clip_sumsq(const float* g, const float* w, const float* l2_elem, const float* lr_scale_elem, size_t n,
+                         float grad_scale, float clip_value, const int64_t* vars, const int64_t* vars_host, int nvars,
+                         const int* blockmap, const int* blockmap_host, int nblocks, double* partials, void* stream);
+int dl3p_grad_clip_finalize(const double* partials, const int64_t* vars, const int64_t* vars_host, int nvars, int nblocks,
+                            int mode, double threshold, float* scale, double* norm, void* stream);
+int dl3p_grad_clip_apply(float* g, const float* w, const float* l2_elem, const float* lr_scale_elem, size_t n,
+                         float grad_scale, float clip_value, const float* scale, const int64_t* vars,
+                         const int64_t* vars_host, int nvars, const int* blockmap, const int* blockmap_host, int nblocks,
+                         double* partials, void* stream);
+
 /* ---------------------------------------------------------------- mixed precision (bf16 storage, fp32 accumulate)
  * train.py:37-46 `--mixed_precision` (the reference sets the Keras global policy; BASELINE.json configs[4] asks for bf16
  * on MobileNetV3-Large 1024x2048).  The *_bf16 entry points are the twins of the calls above for tensors stored as

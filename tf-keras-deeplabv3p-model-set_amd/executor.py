@@ -83,6 +83,7 @@ class ParamStore:
         self.opt_step = torch.zeros(1, dtype=torch.int64, device=device)
         self.l2 = torch.zeros(off, **f)
         self.lr_scale = torch.zeros(off, **f)
+        self._clip_map = None                 # gradient clipping's block map and buffers, built when first asked for (clip_map)
         # transposed copies [N][K] of the pointwise / im2col'd kernels (same offsets as in P): the forward GEMM reads
         # its B fragments from them as 16-B vectors; refreshed after every optimiser step (dl3p_transpose_batch)
         self.Pt = torch.zeros(off, **f)
@@ -212,6 +213,15 @@ class ParamStore:
     def get(self, p, buf=None):
         return self._unpad(p, self.view(p, buf).detach().cpu().numpy())
 
+    def clip_map(self):
+        """the tables and buffers of the dl3p_grad_clip_* calls (ops.GradClipMap), built once: one variable per entry of `offset`
+        (one Keras weight) over its padded length -- the padding has lr_scale 0 and enters nothing.  Which elements are trainable
+        is read from lr_scale by the kernels, so freezing layers changes no table."""
+        if self._clip_map is None:
+            from .ops import GradClipMap
+            self._clip_map = GradClipMap([(self.offset[p], (p.dev_size + 3) // 4 * 4) for p in self.params], self.device)
+        return self._clip_map
+
     def refresh_masks(self):
         """per-element l2 factor and learning-rate multiplier (0 = frozen / not a trainable weight)"""
         l2 = np.zeros(self.total, np.float32)
@@ -271,6 +281,16 @@ def _op_label(op):
     if n is None and getattr(op, 'out', None) is not None:
         n = op.out.name
     return '%s:%s' % (op.kind, n)
+
+
+def clip_launches(clip):
+    """the entry points a clip spec (model clip_spec(): None | (clipvalue, clipnorm, global_clipnorm)) puts in front of the
+    optimiser launch: none without clipping, the apply pass alone for clipvalue alone, else sum of squares, finalize, apply"""
+    if clip is None:
+        return ()
+    if clip[1] is None and clip[2] is None:
+        return ('grad_clip_apply',)
+    return ('grad_clip_sumsq', 'grad_clip_finalize', 'grad_clip_apply')
 
 
 class Plan:
@@ -452,8 +472,11 @@ class BackwardTrace:
 class Executor:
     def __init__(self, graph, head, store, batch, training, num_classes, ignore_index=255, dist=None,
                  seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
-                 averaging=None):
+                 averaging=None, clip=None):
         self.g, self.head, self.store = graph, head, store
+        # gradient clipping: None | (clipvalue, clipnorm, global_clipnorm) (model clip_spec()), traced in front of the optimiser
+        self.clip = clip if training else None
+        self._norm_host, self._norm_evt, self._norm_posted = None, None, None
         self.N, self.training, self.C = batch, training, num_classes
         self.ignore_index = ignore_index
         # loss: ('ce',) | ('weighted', weights[C]) | ('focal', gamma, alpha)  (model.loss_spec)
@@ -2117,6 +2140,12 @@ class Executor:
         if self.dist is not None:
             scale = 1.0 / self.dist.world_size
         kind = self.optimizer[0]
+        l2 = st.l2.data_ptr()
+        if self.clip is not None:
+            # behind the backward plan, which has waited for the gradient collectives: G is the aggregated gradient.  The apply pass
+            # leaves the finished gradient of the whole loss in G, so the optimiser takes it as it is
+            self._trace_clip(P, scale)
+            scale, l2 = 1.0, None
         if self.averaging is not None:
             # the averaging rule in the same pass as the update (dl3p_*_avg), ahead of the mirror refreshes below: after a
             # Lookahead sync every mirror is made from the synced weights
@@ -2125,25 +2154,25 @@ class Executor:
             if kind == 'adam':
                 _, b1, b2, eps = self.optimizer
                 P.k(L.adam_step_avg, st.P.data_ptr(), st.V.data_ptr(), st.V2.data_ptr(), st.G.data_ptr(), st.total,
-                    self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg)
+                    self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, l2, st.lr_scale.data_ptr(), *avg)
             elif kind == 'rmsprop':
                 _, rho, eps = self.optimizer
                 P.k(L.rmsprop_step_avg, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(), rho, eps,
-                    scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
+                    scale, l2, st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
             else:
                 P.k(L.sgd_momentum_avg, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(),
-                    float(self.momentum), 0.0, scale, st.l2.data_ptr(), st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
+                    float(self.momentum), 0.0, scale, l2, st.lr_scale.data_ptr(), *avg, st.opt_step.data_ptr())
         elif kind == 'adam':
             _, b1, b2, eps = self.optimizer
             P.k(L.adam_step, st.P.data_ptr(), st.V.data_ptr(), st.V2.data_ptr(), st.G.data_ptr(), st.total,
-                self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, st.l2.data_ptr(), st.lr_scale.data_ptr())
+                self.lr.data_ptr(), st.opt_step.data_ptr(), b1, b2, eps, scale, l2, st.lr_scale.data_ptr())
         elif kind == 'rmsprop':
             _, rho, eps = self.optimizer
             P.k(L.rmsprop_step, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(), rho, eps,
-                scale, st.l2.data_ptr(), st.lr_scale.data_ptr())
+                scale, l2, st.lr_scale.data_ptr())
         else:
             P.k(L.sgd_momentum, st.P.data_ptr(), st.V.data_ptr(), st.G.data_ptr(), st.total, self.lr.data_ptr(),
-                float(self.momentum), 0.0, scale, st.l2.data_ptr(), st.lr_scale.data_ptr())
+                float(self.momentum), 0.0, scale, l2, st.lr_scale.data_ptr())
         if self.bf16:                       # refresh the bf16 mirrors the next forward / backward read
             P.k(L.f32_to_bf16, st.P.data_ptr(), st.Pb.data_ptr(), st.total)
             if st.tr_table is not None:
@@ -2161,6 +2190,48 @@ class Executor:
             if rb:
                 P.k(L.split_bf16x3_batch, st.P.data_ptr(), st.Sb.data_ptr(), self._sb_tab_b.data_ptr(), len(rb))
         return P
+
+    def _trace_clip(self, P, grad_scale):
+        """clipvalue, then clipnorm or global_clipnorm, on store.G (csrc/grad_clip.hip): clip_launches(self.clip) in this order"""
+        L, st, m = self.L, self.store, self.store.clip_map()
+        value, norm, gnorm = self.clip
+        bufs = (st.P.data_ptr(), st.l2.data_ptr(), st.lr_scale.data_ptr(), st.total, float(grad_scale), float(value or 0.0))
+        tables = m.var_args() + m.block_args()
+        if norm is None and gnorm is None:
+            # the clamp alone: one pass, which also leaves the partial sums last_grad_norm() adds up on the host
+            P.k(L.grad_clip_apply, st.G.data_ptr(), *bufs, None, *tables, m.partials.data_ptr())
+            return
+        P.k(L.grad_clip_sumsq, st.G.data_ptr(), *bufs, *tables, m.partials.data_ptr())
+        P.k(L.grad_clip_finalize, m.partials.data_ptr(), *m.var_args(), m.nblocks, 1 if norm is not None else 2,
+            float(norm if norm is not None else gnorm), m.scale.data_ptr(), m.norm.data_ptr())
+        P.k(L.grad_clip_apply, st.G.data_ptr(), *bufs, m.scale.data_ptr(), *tables, None)
+
+    def _post_grad_norm(self):
+        """start the copy of this step's global gradient norm to pinned host memory behind the optimiser plan (two slots, one event
+        each: the step never waits for the host).  With a norm rule that is norm[nvars]; with clipvalue alone the per-block sums of
+        squares, which last_grad_norm() adds up in float64"""
+        m = self.store.clip_map()
+        src = m.partials[:m.nblocks] if (self.clip[1] is None and self.clip[2] is None) else m.norm[m.nvars:]
+        if self._norm_host is None:
+            self._norm_host = [torch.zeros(src.numel(), dtype=torch.float64, pin_memory=True) for _ in range(2)]
+            self._norm_evt = [torch.cuda.Event(), torch.cuda.Event()]
+            self._norm_k = 0
+        i = self._norm_k & 1
+        self._norm_k += 1
+        self._norm_host[i].copy_(src, non_blocking=True)
+        self._norm_evt[i].record()
+        self._norm_posted = i
+
+    def last_grad_norm(self):
+        """the global gradient norm of the last train_step (None: no clipping, or no step yet); waits for its copy only"""
+        i = self._norm_posted
+        if i is None:
+            return None
+        self._norm_evt[i].synchronize()
+        h = self._norm_host[i].numpy()
+        if self.clip[1] is None and self.clip[2] is None:
+            return float(np.sqrt(np.sum(h, dtype=np.float64)))
+        return float(h[0])
 
     # ---------------------------------------------------------------- running
     def _stage_u8(self, src, slot):
@@ -2263,6 +2334,8 @@ class Executor:
         self.fwd.run()
         self.bwd.run()
         self.opt.run()
+        if self.clip is not None:
+            self._post_grad_norm()
         if self.store.Sb is not None:
             self.store.sb_partial = self
 

@@ -63,14 +63,43 @@ def _register_optional():
 _register_optional()
 
 
-class SGD:
-    """Keras SGD(learning_rate, momentum=0.9, nesterov=False) (common/model_utils.py:124)"""
+def _clip_args(clipnorm, clipvalue, global_clipnorm):
+    """the clipping keywords of a Keras 2.11 legacy OptimizerV2 -> None | (clipvalue, clipnorm, global_clipnorm).  clipnorm and
+    global_clipnorm together raise ValueError as Keras does; a value that is not a positive finite number raises ValueError too
+    (our decision: Keras takes 0 and negative thresholds and then produces zero or sign-flipped gradients)."""
+    if clipnorm is not None and global_clipnorm is not None:
+        raise ValueError('Cannot accept both `clipnorm` and `global_clipnorm`, received clipnorm=%r, global_clipnorm=%r'
+                         % (clipnorm, global_clipnorm))
+    out = []
+    for name, v in (('clipvalue', clipvalue), ('clipnorm', clipnorm), ('global_clipnorm', global_clipnorm)):
+        if v is not None:
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError('%s must be a positive finite number, received %r' % (name, v))
+            if not (v > 0.0 and np.isfinite(v)):
+                raise ValueError('%s must be a positive finite number, received %r' % (name, v))
+        out.append(v)
+    return None if out == [None, None, None] else tuple(out)
 
-    def __init__(self, learning_rate=0.01, momentum=0.9, nesterov=False):
+
+class SGD:
+    """Keras SGD(learning_rate, momentum=0.9, nesterov=False, clipnorm=None, clipvalue=None) (common/model_utils.py:123).
+    clipvalue / clipnorm / global_clipnorm (all three optimisers): the gradient of the whole loss -- regulariser included, after
+    the data-parallel all-reduce, trainable variables only -- is clamped to [-clipvalue, clipvalue], then scaled per variable to
+    an L2 norm of at most clipnorm OR as a whole to a global norm of at most global_clipnorm, on the device
+    (csrc/grad_clip.hip).  Both norms together, or a value that is not a positive finite number, raise ValueError."""
+
+    def __init__(self, learning_rate=0.01, momentum=0.9, nesterov=False, clipnorm=None, clipvalue=None, global_clipnorm=None):
         if nesterov:
             raise ValueError('nesterov momentum is not on the hot path')
+        self._clip = _clip_args(clipnorm, clipvalue, global_clipnorm)
         self.learning_rate, self.momentum = learning_rate, momentum
         self.iterations = 0          # Keras `optimizer.iterations`: a schedule starts at 0 with a NEW optimizer
+
+    def clip_spec(self):
+        """None | (clipvalue, clipnorm, global_clipnorm), None for a rule that is off"""
+        return self._clip
 
     def lr_at(self, step):
         lr = self.learning_rate
@@ -83,9 +112,11 @@ class SGD:
 class Adam(SGD):
     """Keras Adam(learning_rate, epsilon=1e-7, amsgrad=False) (common/model_utils.py:119)"""
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None):
         if amsgrad:
             raise ValueError('amsgrad is not built (the reference passes amsgrad=False)')
+        self._clip = _clip_args(clipnorm, clipvalue, global_clipnorm)
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
         self.momentum = 0.0
         self.iterations = 0
@@ -97,9 +128,11 @@ class Adam(SGD):
 class RMSprop(SGD):
     """Keras RMSprop(learning_rate, rho=0.9, momentum=0.0, centered=False) (common/model_utils.py:121)"""
 
-    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False):
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, clipnorm=None, clipvalue=None,
+                 global_clipnorm=None):
         if momentum or centered:
             raise ValueError('RMSprop momentum / centered are not built (the reference uses momentum=0.0, centered=False)')
+        self._clip = _clip_args(clipnorm, clipvalue, global_clipnorm)
         self.learning_rate, self.rho, self.epsilon = learning_rate, rho, epsilon
         self.momentum = 0.0
         self.iterations = 0
@@ -142,6 +175,9 @@ class _AveragedOptimizer:
 
     def spec(self):
         return self._optimizer.spec()
+
+    def clip_spec(self):
+        return self._optimizer.clip_spec()
 
 
 class MovingAverage(_AveragedOptimizer):
@@ -201,16 +237,19 @@ def get_averaged_optimizer(average_type, optimizer):
     raise ValueError('Unsupported average type')
 
 
-def get_optimizer(optim_type, learning_rate, average_type=None, decay_type=None, decay_steps=100000):
+def get_optimizer(optim_type, learning_rate, average_type=None, decay_type=None, decay_steps=100000, *, clipnorm=None,
+                  clipvalue=None, global_clipnorm=None):
     """common/model_utils.py:112-172: 'sgd' (momentum 0.9), 'adam', 'rmsprop' with the four learning-rate schedules, wrapped
-    by average_type 'ema' | 'swa' | 'lookahead'"""
+    by average_type 'ema' | 'swa' | 'lookahead'; clipnorm / clipvalue / global_clipnorm (the keywords :117-123 spell out as None)
+    go to the optimiser"""
+    clip = dict(clipnorm=clipnorm, clipvalue=clipvalue, global_clipnorm=global_clipnorm)
     optim_type = optim_type.lower()
     if optim_type not in ('sgd', 'adam', 'rmsprop'):
         raise ValueError('Unsupported optimizer type')
     if average_type:
         if not isinstance(average_type, str) or average_type.lower() not in ('ema', 'swa', 'lookahead'):
             raise ValueError('Unsupported average type')
-        return get_averaged_optimizer(average_type, get_optimizer(optim_type, learning_rate, None, decay_type, decay_steps))
+        return get_averaged_optimizer(average_type, get_optimizer(optim_type, learning_rate, None, decay_type, decay_steps, **clip))
     lr = learning_rate
     if decay_type:
         d = decay_type.lower()
@@ -227,10 +266,10 @@ def get_optimizer(optim_type, learning_rate, average_type=None, decay_type=None,
         else:
             raise ValueError('Unsupported lr decay type')
     if optim_type == 'adam':
-        return Adam(lr, epsilon=1e-7)
+        return Adam(lr, epsilon=1e-7, **clip)
     if optim_type == 'rmsprop':
-        return RMSprop(lr, rho=0.9)
-    return SGD(lr, momentum=0.9)
+        return RMSprop(lr, rho=0.9, **clip)
+    return SGD(lr, momentum=0.9, **clip)
 
 
 class SparseCategoricalCrossEntropy(object):
@@ -548,6 +587,7 @@ class DeeplabModel:
         # world-size arithmetic on one GPU with a context whose sum over two identical ranks is a multiplication by 2)
         self.dist = distributed if isinstance(distributed, DistContext) else (DistContext(sync_bn) if distributed else None)
         self._exec = {}
+        self._last_train_ex = None
         if self._store is not None:
             self._store.refresh_masks()
             if not same_optimizer:
@@ -613,9 +653,24 @@ class DeeplabModel:
                 self._store.transpose()
         return self._store
 
+    def _clip_spec(self):
+        spec = getattr(self.optimizer, 'clip_spec', None)
+        return spec() if spec is not None else None
+
+    @property
+    def last_grad_norm(self):
+        """the global L2 norm of the last training step's gradient as the norm rules saw it (the whole loss, trainable variables,
+        after clipvalue, before any norm scaling); None without clipping or before the first step.  The number follows its step to
+        the host asynchronously: reading it waits for that copy, the step itself never does."""
+        ex = getattr(self, '_last_train_ex', None)
+        return ex.last_grad_norm() if ex is not None else None
+
     def _executor(self, batch, training):
         avg = self._avg_spec() if training else None
+        clip = self._clip_spec() if training else None
         key = (batch, training) if avg is None else (batch, training, avg)
+        if clip is not None:
+            key = key + (('clip',) + clip,)
         if key not in self._exec:
             from .executor import Executor
             store = self._ensure_store()
@@ -626,7 +681,7 @@ class DeeplabModel:
                                        ignore_index=ignore, dist=self.dist if training else None,
                                        seed=self.seed + 7919 * rank, loss=loss_spec(self.loss), optimizer=opt,
                                        sample_weighted=getattr(self, 'sample_weight_mode', None) == 'temporal',
-                                       class_counts=getattr(self, '_jaccard', False), averaging=avg)
+                                       class_counts=getattr(self, '_jaccard', False), averaging=avg, clip=clip)
         return self._exec[key]
 
     def train_on_batch(self, x, y, sample_weight=None, return_tensor=False):
@@ -655,6 +710,7 @@ class DeeplabModel:
             if self.use_graphs and not ex.graphed and self._steps_on(ex) >= 1:
                 ex.capture()
             ex.train_step()
+            self._last_train_ex = ex
             if guarded:
                 import torch
                 torch.cuda.synchronize()

@@ -620,6 +620,57 @@ def sgd_momentum(w, v, g, lr_dev, momentum=0.9, l2=0.0, grad_scale=1.0, l2_elem=
                        _p(l2_elem), _p(lr_scale_elem), _stream())
 
 
+class GradClipMap:
+    """the tables of the dl3p_grad_clip_* calls for variables (offset, length) of one flat buffer, in floats and both multiples
+    of 4: `vars` [nvars][3] = {offset, length, first block} and `blockmap` [nblocks][2] = {variable, block within it}, on `device`
+    and (the copies the library checks before it launches) on the host; plus the buffers the three calls share: partials
+    (float64, one per block), scale (float32, one per variable), norm (float64, per variable and, last, the global norm)"""
+
+    def __init__(self, variables, device):
+        import numpy as np
+        per = lib().grad_clip_block_elements()
+        rows, blocks = [], []
+        for v, (off, n) in enumerate(variables):
+            nb = (int(n) + per - 1) // per
+            rows.append((int(off), int(n), len(blocks)))
+            blocks += [(v, b) for b in range(nb)]
+        self.vars_host = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(-1, 3))
+        self.blockmap_host = np.ascontiguousarray(np.array(blocks, dtype=np.int32).reshape(-1, 2))
+        self.nvars, self.nblocks = len(rows), len(blocks)
+        self.vars = torch.from_numpy(self.vars_host).to(device)
+        self.blockmap = torch.from_numpy(self.blockmap_host).to(device)
+        self.partials = torch.zeros(max(self.nblocks, 1), dtype=torch.float64, device=device)
+        self.scale = torch.ones(max(self.nvars, 1), dtype=torch.float32, device=device)
+        self.norm = torch.zeros(self.nvars + 1, dtype=torch.float64, device=device)
+
+    def var_args(self):
+        return self.vars.data_ptr(), self.vars_host.ctypes.data, self.nvars
+
+    def block_args(self):
+        return self.blockmap.data_ptr(), self.blockmap_host.ctypes.data, self.nblocks
+
+
+def grad_clip_sumsq(g, w, cmap, grad_scale=1.0, clip_value=0.0, l2_elem=None, lr_scale_elem=None):
+    """cmap.partials[b] = sum of clamp(g * grad_scale + 2 * l2_elem * w)^2 over the trainable elements of block b"""
+    lib().grad_clip_sumsq(_p(g), _p(w), _p(l2_elem), _p(lr_scale_elem), g.numel(), float(grad_scale), float(clip_value),
+                          *cmap.var_args(), *cmap.block_args(), _p(cmap.partials), _stream())
+
+
+def grad_clip_finalize(cmap, mode, threshold):
+    """cmap.partials -> cmap.norm, cmap.scale; mode 1: threshold / max(norm_v, threshold) per variable, 2: one scale from the
+    global norm"""
+    lib().grad_clip_finalize(_p(cmap.partials), *cmap.var_args(), cmap.nblocks, int(mode), float(threshold), _p(cmap.scale),
+                             _p(cmap.norm), _stream())
+
+
+def grad_clip_apply(g, w, cmap, grad_scale=1.0, clip_value=0.0, l2_elem=None, lr_scale_elem=None, scaled=True, partials=False):
+    """g <- clamp(g * grad_scale + 2 * l2_elem * w) * cmap.scale[variable] in place on the trainable elements (scaled=False: the
+    clamp alone; partials=True: also leave the sums of squares of the clamped gradient in cmap.partials)"""
+    lib().grad_clip_apply(_p(g), _p(w), _p(l2_elem), _p(lr_scale_elem), g.numel(), float(grad_scale), float(clip_value),
+                          _p(cmap.scale) if scaled else None, *cmap.var_args(), *cmap.block_args(),
+                          _p(cmap.partials) if partials else None, _stream())
+
+
 def act_bwd(g, z, act, out, accumulate=False):
     """out (+)= g * act'(z): backward of a bare activation on a materialised tensor"""
     gp, ldg = _pl(g)
