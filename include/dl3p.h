@@ -435,6 +435,26 @@ int dl3p_aug_gridmask_u8(unsigned char* img, unsigned char* label, const int* pa
  * absent here): gray = (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 replicated to three channels; GaussianBlur (5, 5), sigma 0 =
  * [1 4 6 4 1] / 16 separable in 8.8 fixed point, one rounding, BORDER_REFLECT_101. */
 int dl3p_aug_gray_blur_u8(const unsigned char* img, unsigned char* out, const int* flags, int N, int H, int W, void* stream);
+/* The OpenCV steps of the generator (csrc/augment_cv.hip): random_zoom_rotate, random_histeq and the final cv2.resize.  UNPINNED
+ * restatements of OpenCV's published 8-bit arithmetic, like dl3p_aug_gray_blur_u8: cv2 is absent, the kernels are held bit for bit to
+ * tests/cv_rules.py, which states the same rules in NumPy (DESIGN.md section 7 writes them out).  No float64 on the device: the host
+ * computes the per-image tables (augment.warp_tables, augment.resize_tables) and uploads them.
+ * dl3p_aug_warp_nn_u8: cv2.warpAffine(INTER_NEAREST, BORDER_CONSTANT 0) of image and label in one launch, out of place.
+ * tables: N x (2 W + 2 H) ints on the device, per image {adelta[W], bdelta[W], X0[H], Y0[H]} in 22.10 fixed point;
+ * source pixel (sat16((X0[y] + adelta[x]) >> 10), sat16((Y0[y] + bdelta[x]) >> 10)), outside the image -> 0.  flags[n] == 0
+ * copies image n through.  img or label may be NULL.
+ * dl3p_aug_clahe_u8: cvtColor(BGR2YUV), createCLAHE(2.0, (8, 8)).apply on channel 0, cvtColor(YUV2BGR) for the images whose flags[n]
+ * are set (the others are copied).  luts: N x 64 x 256 bytes of workspace on the device.  out may be img.  H, W >= 8.
+ * dl3p_aug_resize_u8: cv2.resize of N images (h, w) -> (H, W), INTER_LINEAR for the image (a copy at equal size, the 2 x 2 area mean
+ * at exactly half size) and INTER_NEAREST for the label.  Source rows are img_pitch / label_pitch bytes apart and image n starts
+ * n * h rows after image 0; the outputs are dense, so `out` may point at a slot of a batch.  tables: 5 W + 5 H ints on the device,
+ * {sx[W], x1[W], a0[W], a1[W], nx[W], sy0[H], sy1[H], b0[H], b1[H], ny[H]} (11-bit weights; nx / ny the nearest source index). */
+int dl3p_aug_warp_nn_u8(const unsigned char* img, unsigned char* out, const unsigned char* label, unsigned char* label_out,
+                        const int* flags, const int* tables, int N, int H, int W, void* stream);
+int dl3p_aug_clahe_u8(const unsigned char* img, unsigned char* out, const int* flags, unsigned char* luts, size_t luts_bytes,
+                      int N, int H, int W, void* stream);
+int dl3p_aug_resize_u8(const unsigned char* img, int img_pitch, unsigned char* out, const unsigned char* label, int label_pitch,
+                       unsigned char* label_out, const int* tables, int N, int h, int w, int H, int W, void* stream);
 /* The label tail of SegmentationGenerator.__getitem__ for byte labels (N images of P pixels each):
  * labels_out = float(label), with label > num_classes-1 replaced by ignore_index (deeplabv3p/data.py:116-121);
  * weights_out (optional) = the `--weighted_type adaptive` pixel weights (data.py:134-145): sklearn's

@@ -10,8 +10,13 @@ map and pinned against PIL itself.
 random_grayscale and random_blur are here as UNPINNED restatements of OpenCV's published 8-bit arithmetic (cv2 is not in this image:
 the kernels are held to oracle/np_augment.py's restatement of the same formulas, not to OpenCV itself).
 
-Not here: random_zoom_rotate, random_histeq and the final cv2.resize -- OpenCV code (warpAffine's fixed-point interpolation tables,
-CLAHE) that cannot be pinned without OpenCV; they stay on the host.
+random_zoom_rotate (cv2.warpAffine, INTER_NEAREST), random_histeq (BGR2YUV, CLAHE on Y, YUV2BGR) and the generator's final cv2.resize
+(`resize`: INTER_LINEAR image, INTER_NEAREST label) are here under the same UNPINNED label (csrc/augment_cv.hip): the rules are written
+out in DESIGN.md section 7 and restated in NumPy by tests/cv_rules.py, which is what the kernels are held to bit for bit.  Their float64
+parts (the inverted rotation matrix, the resize scales) are evaluated here, on the host, into small integer tables that are uploaded
+with the call (warp_tables, resize_tables).
+
+Not here: the decode (PIL, on the host: data.py) and warpAffine / resize with any other interpolation than the reference's.
 """
 import numpy as np
 import torch
@@ -154,20 +159,160 @@ def random_gridmask(images, labels, prob=0.2):
     return gridmask(images, labels, draws)
 
 
-def random_crop(images, labels, crop_shape, prob=.1):
+def random_crop(images, labels, crop_shape, prob=.1, resize_small=False):
     """the crop branch of the reference's random_crop (common/data_utils.py:364-400) for a batch.  DEVIATION, by
     construction: the reference decides `rand() < prob` per image; a batch tensor needs one output shape, so the decision is
     drawn ONCE for the batch.  Within a cropping batch the window of every image is drawn as the reference draws it -- x
     (`randrange(W - crop_w)`) first, then y (data_utils.py:390-391) -- so a seeded `random` yields the reference's windows.
     Returns the inputs unchanged when the draw says no or the window is not smaller than the image (the reference then
-    resizes with cv2, which stays on the host)."""
+    resizes with cv2: `resize`, which resize_small=True applies here, as the generator asks for; called per image, N = 1, this is
+    the reference's function, per-image decision included)."""
     import random
     N, H, W, _ = images.shape
-    if not (rand() < prob) or not (crop_shape[0] < H and crop_shape[1] < W):
+    if not (rand() < prob):
         return images, labels
+    if not (crop_shape[0] < H and crop_shape[1] < W):
+        return resize(images, labels, crop_shape) if resize_small else (images, labels)
     yx = []
     for _ in range(N):
         x = random.randrange(W - crop_shape[1])
         y = random.randrange(H - crop_shape[0])
         yx.append((y, x))
     return flip_crop(images, labels, None, yx, tuple(crop_shape))
+
+
+# ---- the OpenCV steps (csrc/augment_cv.hip).  UNPINNED restatements: see the module docstring
+def _round_i32(v):
+    """cvRound with saturation: round half to even, to int32"""
+    return np.clip(np.rint(v), -2147483648.0, 2147483647.0).astype(np.int64)
+
+
+def warp_tables(H, W, angle, scale):
+    """the 2 W + 2 H integers dl3p_aug_warp_nn_u8 takes for one image, {adelta[W], bdelta[W], X0[H], Y0[H]}: cv2.getRotationMatrix2D
+    about (W // 2, H // 2) in float64, inverted as warpAffine inverts it (its order of operations), then the 22.10 fixed-point column
+    and row terms of the inverse map (the rounding half, 512, goes into the row terms)"""
+    import math
+    a = angle * math.pi / 180.0
+    al, be = scale * math.cos(a), scale * math.sin(a)
+    cx, cy = float(W // 2), float(H // 2)
+    m0, m1, m2, m3, m4, m5 = al, be, (1 - al) * cx - be * cy, -be, al, be * cx + (1 - al) * cy
+    D = m0 * m4 - m1 * m3
+    D = 1.0 / D if D != 0 else 0.0
+    m0, m4 = m4 * D, m0 * D
+    m1 *= -D
+    m3 *= -D
+    m2, m5 = -m0 * m2 - m1 * m5, -m3 * m2 - m4 * m5
+    x, y = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    t = np.concatenate([_round_i32(m0 * x * 1024), _round_i32(m3 * x * 1024), _round_i32((m1 * y + m2) * 1024) + 512,
+                        _round_i32((m4 * y + m5) * 1024) + 512])
+    return t.astype(np.int32)
+
+
+def warp_affine_nn(images, labels, draws):
+    """cv2.warpAffine(flags=INTER_NEAREST, borderMode=BORDER_CONSTANT, borderValue=0) of image and label by the matrix of
+    cv2.getRotationMatrix2D((W // 2, H // 2), angle, scale); draws[n] = None (image copied through) or (angle, scale)"""
+    N, H, W, _ = images.shape
+    assert images.dtype == torch.uint8 and labels.dtype == torch.uint8 and labels.shape == (N, H, W)
+    assert images.is_contiguous() and labels.is_contiguous()
+    dev = images.device
+    tab = np.zeros((N, 2 * W + 2 * H), np.int32)
+    for n, dr in enumerate(draws):
+        if dr is not None:
+            tab[n] = warp_tables(H, W, *dr)
+    fl = torch.as_tensor(np.asarray([0 if dr is None else 1 for dr in draws], np.int32).reshape(N)).to(dev)
+    tab = torch.as_tensor(tab).to(dev)
+    out, lout = torch.empty_like(images), torch.empty_like(labels)
+    lib().aug_warp_nn_u8(images.data_ptr(), out.data_ptr(), labels.data_ptr(), lout.data_ptr(), fl.data_ptr(), tab.data_ptr(), N, H, W,
+                         _stream())
+    return out, lout
+
+
+def random_zoom_rotate(images, labels, rotate_range=30, zoom_range=0.2, prob=0.3):
+    """random_zoom_rotate (common/data_utils.py:241-273) for a batch.  Per image, in the reference's order: random.gauss(0,
+    rotate_range), random.gauss(1, zoom_range) -- both drawn whatever `prob` decides -- then rand() < prob"""
+    import random
+    draws = []
+    for _ in range(images.shape[0]):
+        angle = random.gauss(mu=0.0, sigma=rotate_range) if rotate_range else 0.0
+        scale = random.gauss(mu=1.0, sigma=zoom_range) if zoom_range else 1.0
+        warp = rand() < prob
+        draws.append((angle, scale) if warp and (rotate_range or zoom_range) else None)
+    if all(dr is None for dr in draws):
+        return images, labels
+    return warp_affine_nn(images, labels, draws)
+
+
+def clahe(images, flags, out=None):
+    """cv2.cvtColor(BGR2YUV), cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)).apply on channel 0, cv2.cvtColor(YUV2BGR) for the
+    images whose flags[n] are set; the others are copied.  out may be images"""
+    N, H, W, C = images.shape
+    assert images.dtype == torch.uint8 and C == 3 and images.is_contiguous()
+    if H < 8 or W < 8:
+        raise ValueError('CLAHE on an 8 x 8 tile grid needs H, W >= 8, got %d x %d' % (H, W))
+    fl = torch.as_tensor(np.asarray(flags, np.int32).reshape(N)).to(images.device)
+    out = torch.empty_like(images) if out is None else out
+    luts = torch.empty(N * 64 * 256, dtype=torch.uint8, device=images.device)
+    lib().aug_clahe_u8(images.data_ptr(), out.data_ptr(), fl.data_ptr(), luts.data_ptr(), luts.numel(), N, H, W, _stream())
+    return out
+
+
+def random_histeq(images, size=8, prob=.2):
+    if size != 8:
+        raise ValueError('the device kernel restates CLAHE on the 8 x 8 tile grid (the generator\'s default size)')
+    flags = [1 if rand() < prob else 0 for _ in range(images.shape[0])]
+    if not any(flags):
+        return images
+    return clahe(images, flags)
+
+
+def _linear_axis(dst, src, zero_at_edges):
+    scale = 1.0 / (float(dst) / src)
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = f - s.astype(np.float32)
+    if zero_at_edges:                                       # horizontal: the weight goes to the clamped pixel alone
+        edge = (s < 0) | (s >= src - 1)
+        f = np.where(edge, np.float32(0), f).astype(np.float32)
+        s = np.clip(s, 0, src - 1)
+        s1 = np.minimum(s + 1, src - 1)
+    else:                                                   # vertical: the weights stay, the two rows are clamped
+        s, s1 = np.clip(s, 0, src - 1), np.clip(s + 1, 0, src - 1)
+    w0 = np.clip(np.rint((np.float32(1) - f) * np.float32(2048)), -32768, 32767)
+    w1 = np.clip(np.rint(f * np.float32(2048)), -32768, 32767)
+    nearest = np.minimum(np.floor(np.arange(dst, dtype=np.float64) * scale), src - 1)
+    return [s, s1, w0, w1, nearest]
+
+
+def resize_tables(h, w, H, W):
+    """the 5 W + 5 H integers dl3p_aug_resize_u8 takes, {sx, x1, a0, a1, nx}[W] then {sy0, sy1, b0, b1, ny}[H]: cv2.resize's
+    INTER_LINEAR source indices and 11-bit weights from scale = 1 / (dst / src) in float64 (weights formed in float32), and the
+    INTER_NEAREST indices min(floor(d * scale), src - 1)"""
+    return np.concatenate(_linear_axis(W, w, True) + _linear_axis(H, h, False)).astype(np.int32)
+
+
+def _rows_of(t, row_bytes):
+    """the row pitch in bytes of a (N, h, w[, 3]) uint8 tensor whose rows are dense and whose images follow each other h rows apart"""
+    N, h = t.shape[0], t.shape[1]
+    assert t.dtype == torch.uint8 and (t.dim() == 3 or (t.stride(3) == 1 and t.stride(2) == 3)) and (t.dim() == 4 or t.stride(2) == 1)
+    pitch = t.stride(1)
+    assert pitch >= row_bytes and (N == 1 or t.stride(0) == h * pitch), 'resize: images must lie h rows apart'
+    return pitch
+
+
+def resize(images, labels, shape, out=None):
+    """cv2.resize(image, shape[::-1]) (INTER_LINEAR) and cv2.resize(label, shape[::-1], interpolation=INTER_NEAREST) for a batch;
+    shape = (H, W).  The inputs may be row-pitched views (a crop window).  out = (images_out, labels_out): dense uint8 tensors of
+    N * H * W * 3 and N * H * W bytes to write into, e.g. one slot of a batch; made here when None"""
+    N, h, w, _ = images.shape
+    H, W = shape
+    assert labels.shape == (N, h, w)
+    dev = images.device
+    if out is None:
+        out = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev), torch.empty((N, H, W), dtype=torch.uint8, device=dev))
+    oi, ol = out
+    assert oi.dtype == torch.uint8 and ol.dtype == torch.uint8 and oi.is_contiguous() and ol.is_contiguous()
+    assert oi.numel() == N * H * W * 3 and ol.numel() == N * H * W
+    tab = torch.as_tensor(resize_tables(h, w, H, W)).to(dev)
+    lib().aug_resize_u8(images.data_ptr(), _rows_of(images, 3 * w), oi.data_ptr(), labels.data_ptr(), _rows_of(labels, w), ol.data_ptr(),
+                        tab.data_ptr(), N, h, w, H, W, _stream())
+    return oi, ol

@@ -462,6 +462,12 @@ class BatchFeeder:
     def put(self, x, y=None, sample_weight=None):
         slot = self.k & 1
         self.k += 1
+        if getattr(x, 'is_cuda', False):
+            # a batch made on the device (data.SegmentationGenerator, output='device'): nothing crosses PCIe, no pinned copy; the step
+            # waits for the work that built it, which is whatever the current stream holds now
+            import torch
+            self.ready[slot].record(torch.cuda.current_stream())
+            return StagedBatch(slot, x, y, sample_weight)
         self.ready[slot].synchronize()          # (the DMA that last read this slot's pinned buffers; long done)
         if self.free[slot] is not None:
             self.stream.wait_event(self.free[slot])
@@ -742,9 +748,10 @@ class DeeplabModel:
         """probabilities (B,H*W,C) for a training-shaped model, (B,H,W,C) otherwise (eval.py:33-36)"""
         if isinstance(x, (list, tuple)):
             x = x[0]
-        x = np.asarray(x)
-        if x.dtype != np.uint8:                 # uint8 pixels are normalised on the device (Executor.set_inputs)
-            x = x.astype(np.float32, copy=False)
+        if not _on_device_u8(x):                # (CUDA uint8 tensors go to set_inputs as they are)
+            x = np.asarray(x)
+            if x.dtype != np.uint8:             # uint8 pixels are normalised on the device (Executor.set_inputs)
+                x = x.astype(np.float32, copy=False)
         B = x.shape[0]
         ex = self._executor(B, False)
         ex.set_inputs(x)
@@ -957,6 +964,12 @@ class DeeplabModel:
             self.set_weights([data[p.name] for p in self._keras_params()])
 
 
+def _on_device_u8(a):
+    """a CUDA uint8 tensor: what data.SegmentationGenerator(output='device') yields"""
+    import torch
+    return isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.uint8
+
+
 def _evaluate(self, gen, steps=None):
     """Keras `evaluate` / the validation pass of `fit`: mean of the compiled loss with inference-mode BN and no dropout,
     evaluated on the device (the probability tensor is neither written nor downloaded); fills last_val_metrics"""
@@ -964,11 +977,18 @@ def _evaluate(self, gen, steps=None):
     n = steps or len(gen)
     tot, cnt, jac = 0.0, 0, []
     for i in range(n):
-        x, y = np.asarray(gen[i][0]), np.asarray(gen[i][1])
-        B = x.shape[0]
-        ex = self._executor(B, False)
-        ex.set_inputs(x if x.dtype == np.uint8 else x.astype(np.float32, copy=False),
-                      y if y.dtype == np.uint8 else y.astype(np.float32, copy=False))
+        first = gen[i]
+        if _on_device_u8(first[0]):             # a device generator: one fetch, the CUDA uint8 tensors as they are
+            x, y = first[0], first[1]
+            B = x.shape[0]
+            ex = self._executor(B, False)
+            ex.set_inputs(x, y)
+        else:                                   # (host arrays: images of one fetch, labels of a second, as ever)
+            x, y = np.asarray(first[0]), np.asarray(gen[i][1])
+            B = x.shape[0]
+            ex = self._executor(B, False)
+            ex.set_inputs(x if x.dtype == np.uint8 else x.astype(np.float32, copy=False),
+                          y if y.dtype == np.uint8 else y.astype(np.float32, copy=False))
         counts = None
         if getattr(self, '_jaccard', False):
             counts = torch.zeros((B, 3, self.num_classes), dtype=torch.int32, device='cuda')
@@ -1014,10 +1034,14 @@ def _evaluate_miou(self, gen, steps=None, class_names=None, verbose=0):
     cm = torch.zeros(C * C, dtype=torch.int64, device='cuda')
     for i in range(n):
         batch = gen[i]
-        x, y = np.asarray(batch[0]), np.asarray(batch[1])
-        ex = self._executor(x.shape[0], False)
-        ex.set_inputs(x if x.dtype == np.uint8 else x.astype(np.float32, copy=False),
-                      y if y.dtype == np.uint8 else y.astype(np.float32, copy=False))
+        if _on_device_u8(batch[0]):
+            ex = self._executor(batch[0].shape[0], False)
+            ex.set_inputs(batch[0], batch[1])
+        else:
+            x, y = np.asarray(batch[0]), np.asarray(batch[1])
+            ex = self._executor(x.shape[0], False)
+            ex.set_inputs(x if x.dtype == np.uint8 else x.astype(np.float32, copy=False),
+                          y if y.dtype == np.uint8 else y.astype(np.float32, copy=False))
         ex.eval_step(cm)
     res = miou_from_confusion(cm.view(C, C).cpu().numpy(), class_names)
     if verbose:
