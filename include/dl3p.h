@@ -361,6 +361,13 @@ int dl3p_bn_finalize(const float* partials, int rows, const double* sums, int C,
                      const float* gamma, const float* beta, float eps, float momentum,
                      float* moving_mean, float* moving_var, int update_moving,
                      float* scale, float* shift, float* save_mean, float* save_invstd, void* stream);
+/* dl3p_bn_finalize for a BatchNorm that runs in front of a folded nearest upsampling (Fast-SCNN): the sums and `count` are
+ * those of the small map (same mean and biased variance as the replicated one), `moving_count` = the element count of the tensor
+ * Keras normalises, which Bessel's factor of update_moving == 2 is taken from.  moving_count >= count. */
+int dl3p_bn_finalize_counts(const float* partials, int rows, const double* sums, int C, double count, double moving_count,
+                            const float* gamma, const float* beta, float eps, float momentum,
+                            float* moving_mean, float* moving_var, int update_moving,
+                            float* scale, float* shift, float* save_mean, float* save_invstd, void* stream);
 /* inference-mode coefficients from the moving statistics */
 int dl3p_bn_infer_coeffs(const float* gamma, const float* beta, const float* moving_mean,
                          const float* moving_var, float eps, float* scale, float* shift,
@@ -904,6 +911,52 @@ size_t dl3p_deconv2x2_bwd_weight_workspace(int N, int H, int W, int Cin, int Cou
 int dl3p_deconv2x2_bwd_weight(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const float* dy,
                               int lddy, float* gw, float* gb, float* workspace, size_t workspace_bytes, int N, int H, int W,
                               int Cin, int Cout, void* stream);
+
+/* ---------------------------------------------------------------- nearest upsampling (Fast-SCNN, csrc/nearest.hip, csrc/nearest_head.hip)
+ * UpSampling2D((r, r)) (fast_scnn/models/fast_scnn.py:116,143) replicates every pixel r x r times.  Pointwise convs, bias, ReLU and
+ * training-mode BatchNorm commute with it and a dilation-r depthwise conv of the replicated map is the replicated dilation-1 conv of
+ * the small one, so the graph runs such chains at the low resolution and meets the full resolution in these kernels only.  All of
+ * them: fp32, NHWC, C % 4 == 0, 16-byte aligned bases, ld % 4 == 0 and ld >= C (inputs and outputs may be channel slices), 64-bit
+ * offsets, 1 <= r <= 8, H == r * h and W == r * w (DL3P_EINVAL otherwise), gather forms without floating-point atomics.
+ * dl3p_upsample_add_fwd: out[n,y,x,c] = act_a(a[n,y,x,c] * a_scale + a_shift) + act_b(b[n,y/r,x/r,c] * b_scale + b_shift), a and out
+ * (N,H,W,C), b (N,h,w,C); scale and shift come together or not at all.  stat_partials (or NULL): [*rows_out][2][C] partial rows of
+ * the per-channel sum and sum of squares of `out`, the layout dl3p_bn_reduce_partials / dl3p_bn_finalize consume
+ * (rows <= DL3P_MAX_STAT_ROWS).
+ * dl3p_block_sum_bwd: g_low[n,y,x,c] (+)= sum over i, j < r of g[n,r*y+i,r*x+j,c] in (i, j) order -- the gradient w.r.t. the
+ * (activated) small operand b above, and of every tensor computed at low resolution in place of its replicated twin. */
+int dl3p_upsample_add_fwd(const float* a, int lda, const float* a_scale, const float* a_shift, int a_act, const float* b, int ldb,
+                          const float* b_scale, const float* b_shift, int b_act, float* out, int ldo, float* stat_partials,
+                          int* rows_out, int N, int h, int w, int C, int H, int W, int r, void* stream);
+int dl3p_block_sum_bwd(const float* g, int ldg, float* g_low, int ldgl, int accumulate, int N, int h, int w, int C, int H, int W,
+                       int r, void* stream);
+/* AveragePooling2D(pool_size=(kh, kw), strides=(kh, kw), 'valid') with large, possibly rectangular windows (the pyramid pooling
+ * block, fast_scnn.py:67-83): Ho = H / kh, Wo = W / kw (floor), 1 <= kh, kw <= 128; the mean of the kh*kw taps of the (lazily
+ * activated) input.  Windows of up to 16 taps are summed by one thread in (ky, kx) order; larger ones by a workgroup whose pixel lanes
+ * walk the taps with a fixed stride and are combined in lane order (deterministic).  Backward: gx (+)= dy[iy / kh][ix / kw] / (kh*kw),
+ * the gradient w.r.t. the activated input; rows and columns no window covers get 0 (are left alone with accumulate).  dl3p_avgpool2d_*
+ * keeps serving the overlapping / small windows. */
+int dl3p_winpool2d_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, float* y, int ldy, int N,
+                       int H, int W, int C, int kh, int kw, int Ho, int Wo, void* stream);
+int dl3p_winpool2d_bwd(const float* dy, int lddy, float* gx, int ldgx, int accumulate, int N, int H, int W, int C, int kh, int kw,
+                       int Ho, int Wo, void* stream);
+/* The head behind UpSampling2D((r, r)) + Reshape + Softmax 'pred_mask' (fast_scnn.py:143-149): the logits z [N,h,w,ldz] reach
+ * (H, W) = (r h, r w) by replication, so ONE softmax per logit pixel serves its r x r block; no (N,H,W,.) logit or gradient tensor
+ * exists.  Labels, ignore_index, inv_count, loss kinds, class weights, focal parameters and pixel weights mean what they mean for
+ * dl3p_upsample_softmax_loss (labels and pixel weights are full-resolution, [N*H*W]).  1 <= C <= 256, ldz and ldgz >= C rounded up to 4.
+ * dl3p_nearest_softmax_probs: probs (N,H,W,C) compact, as Keras returns it.
+ * dl3p_nearest_head_train: loss_partials[*rows_out] (scaled by inv_count; sum them with dl3p_reduce_rows) and, with gz != NULL,
+ * gz[n,y,x,:] (+)= sum over the block's labels k of f_k * inv_count * (p - onehot(y_k)), pad channels [C, C rounded up to 4) = 0.
+ * dl3p_nearest_argmax_confusion / dl3p_nearest_class_counts: as dl3p_argmax_confusion / dl3p_class_counts, the class of a full-
+ * resolution pixel being the argmax of its logit pixel (first index on ties). */
+int dl3p_nearest_softmax_probs(const float* z, int ldz, float* probs, int N, int h, int w, int C, int H, int W, void* stream);
+int dl3p_nearest_head_train(const float* z, int ldz, const float* labels, int ignore_index, float inv_count, int loss_kind,
+                            const float* class_weights, float focal_gamma, float focal_alpha, const float* pixel_weights,
+                            float* gz, int ldgz, int accumulate, float* loss_partials, int* rows_out, int N, int h, int w, int C,
+                            int H, int W, void* stream);
+int dl3p_nearest_argmax_confusion(const float* z, int ldz, const float* labels, int32_t* pred_mask,
+                                  unsigned long long* confusion, int N, int h, int w, int C, int H, int W, void* stream);
+int dl3p_nearest_class_counts(const float* z, int ldz, const float* labels, int32_t* counts, int N, int h, int w, int C, int H,
+                              int W, void* stream);
 
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP

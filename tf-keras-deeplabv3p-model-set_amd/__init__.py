@@ -5,7 +5,7 @@ importlib:  importlib.import_module('tf-keras-deeplabv3p-model-set_amd')  -- or 
 `deeplabv3p` shim package at the repo root, which mirrors the reference's import paths
 (`from deeplabv3p.model import get_deeplabv3p_model`).
 """
-from .model import (get_deeplabv3p_model, get_unet_model, deeplab_model_map, DeeplabModel, SGD, Adam, RMSprop, get_optimizer,  # noqa: F401
+from .model import (get_deeplabv3p_model, get_unet_model, get_fast_scnn_model, deeplab_model_map, DeeplabModel, SGD, Adam, RMSprop, get_optimizer,  # noqa: F401
                     SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy, SparseSoftmaxFocalLoss,
                     miou_from_confusion, Jaccard, jaccard_from_counts, EvalCallBack, MovingAverage, SWA, Lookahead,
                     AverageModelCheckpoint)
@@ -14,7 +14,7 @@ from .data import SegmentationGenerator  # noqa: F401,E402
 from . import mixed_precision  # noqa: F401,E402
 from . import watchdog  # noqa: F401,E402
 
-__all__ = ['get_deeplabv3p_model', 'get_unet_model', 'deeplab_model_map', 'DeeplabModel', 'SGD', 'Adam', 'RMSprop', 'get_optimizer',
+__all__ = ['get_deeplabv3p_model', 'get_unet_model', 'get_fast_scnn_model', 'deeplab_model_map', 'DeeplabModel', 'SGD', 'Adam', 'RMSprop', 'get_optimizer',
            'SparseCategoricalCrossEntropy', 'WeightedSparseCategoricalCrossEntropy', 'SparseSoftmaxFocalLoss',
            'miou_from_confusion', 'Jaccard', 'jaccard_from_counts', 'EvalCallBack', 'MovingAverage', 'SWA', 'Lookahead',
            'AverageModelCheckpoint', 'SegmentationGenerator', 'mixed_precision']

@@ -433,7 +433,7 @@ __device__ __forceinline__ void reduce2_rows(const float* partials, int rows, co
 }
 
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials, int rows, const double* sums, int C,
-                                                          double count, const float* gamma, const float* beta,
+                                                          double count, double moving_count, const float* gamma, const float* beta,
                                                           float eps, float momentum, float* moving_mean,
                                                           float* moving_var, int update_moving, float* scale,
                                                           float* shift, float* save_mean, float* save_invstd) {
@@ -463,7 +463,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials
       // SyncBatchNormalization, layers.py:65-66); 2: Bessel-corrected, count / (count - 1) (the fused FusedBatchNormV3 kernel
       // behind plain BatchNormalization, layers.py:68 -- what the string compare at layers.py:64 selects under the pinned
       // tensorflow==2.11.0)
-      const double mvar = (update_moving == 2 && count > 1.0) ? var * (count / (count - 1.0)) : var;
+      // (moving_count: the element count Bessel's factor is taken from -- `count` itself except behind a folded nearest upsampling,
+      // dl3p_bn_finalize_counts)
+      const double mvar = (update_moving == 2 && moving_count > 1.0) ? var * (moving_count / (moving_count - 1.0)) : var;
       moving_mean[c] = mm * momentum + (float)mean * (1.f - momentum);
       moving_var[c] = mv * momentum + (float)mvar * (1.f - momentum);
     }
@@ -479,9 +481,24 @@ extern "C" int dl3p_bn_finalize(const float* partials, int rows, const double* s
                  "dl3p_bn_finalize: bad arguments");
   DL3P_CHECK_ARG(!update_moving || (moving_mean && moving_var), "dl3p_bn_finalize: moving stats missing");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, FIN_CX)), dim3(FIN_CX * FIN_RY), 0, (hipStream_t)stream, partials, rows,
-                     sums, C, count, gamma, beta, eps, momentum, moving_mean, moving_var, update_moving, scale, shift,
+                     sums, C, count, count, gamma, beta, eps, momentum, moving_mean, moving_var, update_moving, scale, shift,
                      save_mean, save_invstd);
   DL3P_CHECK_LAUNCH("dl3p_bn_finalize");
+  return DL3P_OK;
+}
+
+extern "C" int dl3p_bn_finalize_counts(const float* partials, int rows, const double* sums, int C, double count,
+                                       double moving_count, const float* gamma, const float* beta, float eps, float momentum,
+                                       float* moving_mean, float* moving_var, int update_moving, float* scale, float* shift,
+                                       float* save_mean, float* save_invstd, void* stream) {
+  DL3P_CHECK_ARG((partials && rows > 0) || sums, "dl3p_bn_finalize_counts: need partial rows or sums");
+  DL3P_CHECK_ARG(C > 0 && count > 0 && moving_count >= count && gamma && beta && scale && shift && save_mean && save_invstd,
+                 "dl3p_bn_finalize_counts: bad arguments (moving_count must be at least count)");
+  DL3P_CHECK_ARG(!update_moving || (moving_mean && moving_var), "dl3p_bn_finalize_counts: moving stats missing");
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, FIN_CX)), dim3(FIN_CX * FIN_RY), 0, (hipStream_t)stream, partials, rows,
+                     sums, C, count, moving_count, gamma, beta, eps, momentum, moving_mean, moving_var, update_moving, scale, shift,
+                     save_mean, save_invstd);
+  DL3P_CHECK_LAUNCH("dl3p_bn_finalize_counts");
   return DL3P_OK;
 }
 

@@ -65,6 +65,9 @@ class ParamStore:
         self.total = off
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros(off, **f)
+        # (a slice of G belongs to the ONE launch that writes that parameter's gradient; a parameter whose gradient no launch produces --
+        # Executor._bias_grad: a bias that a training-mode BatchNorm cancels -- keeps the 0 it is given in _begin_backward.  Everything
+        # that works on G in place, the all-reduce and the clip, maps 0 to 0)
         self.G = torch.zeros(off, **f)
         self.V = torch.zeros(off, **f)
         self.V2 = None                        # second-moment buffer, allocated when Adam asks for it
@@ -664,9 +667,22 @@ class Executor:
                      self.class_weights is None and zt is not None and zt.requires_grad)
         # (the logits and their gradient stay fp32 under the bf16 policy -- _is_f32 -- so the separable head serves it too; the padded
         # classes of the gradient buffer are never written by anyone and keep the zeros they were allocated with)
+        # UpSampling2D((r, r)) in front of the softmax (Fast-SCNN): the dl3p_nearest_* head, one softmax per logit pixel.  Its
+        # training kernel serves every loss and writes d loss / d logits itself, like the fused bilinear heads
+        self.nearest_head = getattr(g, 'head_upsample', 'bilinear') == 'nearest'
+        plain = plain and not self.nearest_head
         self.fused_head_rows = bool(plain and want == 'rows' and L.head_train_rows_supported(zt.H, zt.W, self.C, H, W))
         self.fused_head = self.fused_head_rows or bool(plain and not self.bf16 and want not in ('0', 'rows') and
                                                        L.head_train_supported(zt.H, zt.W, self.C, H, W))
+        self.fused_head = self.fused_head or bool(self.nearest_head and self.training and zt.requires_grad)
+        # depthwise-conv biases carried through their BatchNorm ('bn_bias' ops): per-channel constants of the two small launches
+        self._bias_aux = {}
+        for op in g.ops:
+            if op.kind == 'bn' and getattr(op.bn, 'count_scale', 1) != 1:
+                assert not self.sync_bn, 'a BatchNorm in front of a folded upsampling: local statistics only'
+            if op.kind == 'bn_bias':
+                assert not self.sync_bn and not self.bf16, 'a depthwise bias in front of a BatchNorm: fp32, local statistics only'
+                self._bias_aux[op] = (torch.full((op.bn.C,), 1.0 - op.bn.momentum, **self.f32), torch.zeros(op.bn.C, **self.f32))
         self.head_wsb = L.head_train_rows_workspace(N, zt.H, zt.W, self.C, H, W) if self.fused_head_rows else 0
         self.head_ws = torch.zeros(self.head_wsb // 4, **self.f32) if self.fused_head_rows else None
         self.dlogits_big = (torch.zeros(N * H * W * self.cpad, **self.f32)
@@ -895,7 +911,7 @@ class Executor:
             e, b, d = self._irb_expand.get(op) or self._irb_dw[op]
             xt = e.x.tensor
             return L.irb_bwd_workspace(1 if op is e else 0, N, xt.H, xt.W, e.cin, e.cout, d.stride, d.pad_t, d.pad_l)
-        if getattr(op, 'b', None) is not None or self._rows(op) <= 64:
+        if self._bias_grad(op) is not None or self._rows(op) <= 64:
             return 0
         if r == R_DW:
             return (L.dwconv2d_bwd_weight_workspace_bf16 if self.bf16 else L.dwconv2d_bwd_weight_workspace)(N, op.Ho, op.Wo, op.c, op.k)
@@ -910,6 +926,17 @@ class Executor:
         if r == R_GEMM:
             return L.conv2d_gemm_bwd_weight_workspace(N, op.Ho, op.Wo, op.cin, op.cout, op.k)
         return 0
+
+    def _bias_grad(self, op):
+        """the bias whose gradient a conv's weight-gradient launch has to produce.  None without a bias -- and None where the graph
+        says that a training-mode BatchNorm removes the bias again (op.bias_bn, the Fast-SCNN convs): d loss / d bias is then
+        exactly 0, the sum of a dz that BatchNorm backward has centred, and a launch would return its fp32 cancellation noise.
+        The gradient buffer keeps the 0 it is given in _begin_backward; the optimiser still applies the bias' l2 term"""
+        b = getattr(op, 'b', None)
+        bb = getattr(op, 'bias_bn', None)
+        if b is not None and bb is not None and self.training and bb.layer.trainable and not self.sync_bn:
+            return None
+        return b
 
     def _reduce_all(self, P, jobs):
         """one dl3p_reduce_rows_batched call for every (slabs, destination, rows, n) job of the step"""
@@ -970,8 +997,10 @@ class Executor:
                 setrg(op.z, op.layer.trainable)
             elif k == 'materialize':
                 setrg(op.out, rg(op.x) or (op.r is not None and rg(op.r)))
-            elif k in ('gap', 'resize', 'broadcast', 'maxpool', 'avgpool'):
+            elif k in ('gap', 'resize', 'broadcast', 'maxpool', 'avgpool', 'winpool'):
                 setrg(op.out, rg(op.x))
+            elif k == 'up_add':
+                setrg(op.out, rg(op.x) or rg(op.r))
             elif k == 'se_mul':
                 setrg(op.out, rg(op.x) or rg(op.s))
         for (t, act, vt) in self.g.act_views.values():
@@ -1119,6 +1148,32 @@ class Executor:
                 xt, t = op.x.tensor, op.out
                 P.k(L.avgpool2d_fwd_bf16 if self.bf16 else L.avgpool2d_fwd, *self.vargs(op.x), self.tptr(t), t.ld, N,
                     xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
+            elif k == 'winpool':
+                xt, t = op.x.tensor, op.out
+                P.k(L.winpool2d_fwd, *self.vargs(op.x), self.tptr(t), t.ld, N, xt.H, xt.W, xt.C, op.kh, op.kw, op.Ho, op.Wo)
+            elif k == 'up_add':
+                # Add([a, UpSampling2D(r)(b)]) and the statistics of the BatchNorm behind it in one launch (csrc/nearest.hip)
+                t, bt = op.out, op.r.tensor
+                want = train and op.bn is not None and op.bn.layer.trainable
+                rows = ctypes.c_int(0)
+                P.k(L.upsample_add_fwd, *self.vargs(op.x), *self.vargs(op.r), self.tptr(t), t.ld,
+                    self.partials.data_ptr() if want else None, ctypes.byref(rows), N, bt.H, bt.W, t.C, t.H, t.W, op.factor, tag=op.name)
+                op.rows = rows.value
+            elif k == 'bn_bias':
+                # the bias b of the depthwise conv in front of this BatchNorm is never added to z: training-mode BatchNorm removes
+                # it again.  What it leaves behind: the batch mean that feeds the moving mean is mean(z) + b, and the inference
+                # shift beta - (moving_mean - b) * scale
+                bn = op.bn
+                lp = {p.key: p for p in bn.layer.params}
+                one_m, zeros = self._bias_aux[op]
+                sp, hp = self._bn_coeffs(bn)
+                if train and bn.layer.trainable:
+                    mm = st.ptr(lp['moving_mean'])
+                    P.k(L.affine_act, mm, bn.C, None, None, ACT_NONE, st.ptr(op.bias), bn.C, one_m.data_ptr(), zeros.data_ptr(),
+                        ACT_NONE, 0.0, 0, self.step.data_ptr(), mm, bn.C, 1, bn.C)
+                else:
+                    P.k(L.affine_act, st.ptr(op.bias), bn.C, sp, hp, ACT_NONE, None, 0, None, None, ACT_NONE, 0.0, 0,
+                        self.step.data_ptr(), hp, bn.C, 1, bn.C)
             elif k == 'se_mul':
                 s_ptr, lds, _, _, sact = self.vargs(op.s)
                 t = op.out
@@ -1143,6 +1198,22 @@ class Executor:
         L, N, train = self.L, self.N, self.training
         zt = self.head.tensor
         rows = ctypes.c_int(0)
+        if self.nearest_head:
+            if train:
+                P.k(L.nearest_head_train, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
+                    1.0 / float(N * self.H * self.W), self.loss_kind,
+                    None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma, self.loss_alpha,
+                    None if self.pixel_weights is None else self.pixel_weights.data_ptr(),
+                    self.tptr(zt, True) if zt.requires_grad else None, zt.ld, 0, self.loss_partials.data_ptr(), ctypes.byref(rows),
+                    N, zt.H, zt.W, self.C, self.H, self.W)
+                P.k(L.reduce_rows, self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0)
+            else:
+                P.k(L.nearest_softmax_probs, self.tptr(zt), zt.ld, self.probs.data_ptr(), N, zt.H, zt.W, self.C, self.H, self.W)
+            if train and self.metric_counts is not None:
+                P.k(L.fill, self.metric_counts.data_ptr(), 0.0, N * 3 * self.C)
+                P.k(L.nearest_class_counts, self.tptr(zt), zt.ld, self.labels.data_ptr(), self.metric_counts.data_ptr(), N, zt.H,
+                    zt.W, self.C, self.H, self.W)
+            return
         if train and self.fused_head:
             # loss + d loss / d (conv_upsample output) in one launch; the full-resolution gradient is never written
             ws = (self.head_ws.data_ptr(), self.head_wsb) if self.fused_head_rows else ()
@@ -1289,6 +1360,10 @@ class Executor:
         elif self.training and bn.layer.trainable and op in self._irb_bn:
             e = self._irb_bn[op][0]
             P.k(L.irb_bn_finalize_cov, self.irb_cov_sums.data_ptr(), st.ptr(e.w), e.cin, e.cout, *self._bn_finalize_args(bn, count))
+        elif self.training and bn.layer.trainable and getattr(bn, 'count_scale', 1) != 1:
+            # in front of a folded UpSampling2D: Bessel's factor from the element count of the tensor Keras normalises
+            tail = self._bn_finalize_args(bn, count)
+            P.k(L.bn_finalize_counts, self.partials.data_ptr(), op.producer.rows, None, bn.C, count, count * bn.count_scale, *tail[1:])
         elif self.training and bn.layer.trainable:
             P.k(L.bn_finalize, self.partials.data_ptr(), op.producer.rows, None, bn.C, *self._bn_finalize_args(bn, count))
         else:
@@ -1431,6 +1506,9 @@ class Executor:
         """what one backward trace decides up front: the BatchNorms whose backward sums ride on a data gradient, how weight
         gradients are issued (deferred, as slabs) and the workspaces that takes.  -> the gradient bucket edges"""
         T.ws, T.wsb = self.workspace.data_ptr(), self.workspace.numel() * 4
+        for op in self.g.ops:
+            if getattr(op, 'b', None) is not None and self._bias_grad(op) is None:
+                self.store.view(op.b, self.store.G).zero_()
         # data parallel: the flat gradient buffer is produced back to front; each finished bucket is
         # all-reduced on the side stream while the remaining backward kernels run
         bucket_edges = self._bucket_edges() if self.dist is not None else {}
@@ -1594,7 +1672,7 @@ class Executor:
         r = self._bwd_route(op)
         x = self.vargs(op.x)
         gw = st.ptr(op.w, st.G)
-        b = getattr(op, 'b', None)
+        b = self._bias_grad(op)
         gb = st.ptr(b, st.G) if b else None
         if r == R_PW:
             self._wgrad(P, L.pwconv_bwd_weight, *x, dz, lddz, gw, gb, T.ws, T.wsb, *self._mkn(op))
@@ -1730,6 +1808,30 @@ class Executor:
         out, xt = op.out, op.x.tensor
         P.k(self.L.avgpool2d_bwd_bf16 if self.bf16 else self.L.avgpool2d_bwd, self.tptr(out, True), out.ld,
             *self._gbuf_acc(op.x), self.N, xt.H, xt.W, xt.C, op.k, op.stride, op.Ho, op.Wo)
+
+    def _backward_winpool(self, P, op):
+        # d/d(activated input) of the window average pooling; rows and columns no window covers get 0
+        out, xt = op.out, op.x.tensor
+        P.k(self.L.winpool2d_bwd, self.tptr(out, True), out.ld, *self._gbuf_acc(op.x), self.N, xt.H, xt.W, xt.C, op.kh, op.kw,
+            op.Ho, op.Wo)
+
+    def _backward_up_add(self, P, op):
+        """Add([a, UpSampling2D(r)(b)]): d/d(a) is the gradient of the sum (read in place by a's BatchNorm where the Add is its only
+        reader, like a residual Add's), d/d(b) its r x r block sum"""
+        T, out, L = self._bt, op.out, self.L
+        gt, ldt = self.tptr(out, True), out.ld
+        at, bt = op.x.tensor, op.r.tensor
+        if at.requires_grad or at.root.requires_grad:
+            xb = T.bn_of.get(id(at)) if op.x.bn is not None else None
+            if (T.alias_ok and xb is not None and getattr(op.x, 'view_grad', None) is None and at.C == out.C
+                    and T.readers.get(xb) == {op} and at.id not in T.written and (at.base is None or at.base.id not in T.written)):
+                T.galias[at.id] = (gt, ldt)
+                T.written.add(at.id)
+            else:
+                gp, ldg, keyt = self._gbuf(op.x)
+                P.k(L.scale_mask_bwd, gt, ldt, 0.0, 0, None, gp, ldg, self._acc(keyt), self.N * out.H * out.W, out.C)
+        if bt.requires_grad or bt.root.requires_grad:
+            P.k(L.block_sum_bwd, gt, ldt, *self._gbuf_acc(op.r), self.N, bt.H, bt.W, out.C, out.H, out.W, op.factor)
 
     def _backward_gap(self, P, op):
         out, xt = op.out, op.x.tensor
@@ -2357,7 +2459,7 @@ class Executor:
         self._sb_sync()
         self._eval_plan.run()
         zt = self.head.tensor
-        self.L.argmax_confusion(self.tptr(zt), zt.ld, None if confusion is None else self.labels.data_ptr(),
+        (self.L.nearest_argmax_confusion if self.nearest_head else self.L.argmax_confusion)(self.tptr(zt), zt.ld, None if confusion is None else self.labels.data_ptr(),
                                 None if pred is None else pred.data_ptr(),
                                 None if confusion is None else confusion.data_ptr(), self.N, zt.H, zt.W, self.C, self.H,
                                 self.W, torch.cuda.current_stream().cuda_stream)
@@ -2376,15 +2478,22 @@ class Executor:
         zt, L = self.head.tensor, self.L
         st = torch.cuda.current_stream().cuda_stream
         rows = ctypes.c_int(0)
-        L.upsample_softmax_loss(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
-                                1.0 / float(self.N * self.H * self.W), self.loss_kind,
-                                None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,
-                                self.loss_alpha, None, None, None, None, self.cpad, self.loss_partials.data_ptr(),
-                                ctypes.byref(rows), self.N, zt.H, zt.W, self.C, self.H, self.W, st)
+        if self.nearest_head:
+            L.nearest_head_train(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
+                                 1.0 / float(self.N * self.H * self.W), self.loss_kind,
+                                 None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,
+                                 self.loss_alpha, None, None, 0, 0, self.loss_partials.data_ptr(), ctypes.byref(rows), self.N, zt.H,
+                                 zt.W, self.C, self.H, self.W, st)
+        else:
+            L.upsample_softmax_loss(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
+                                    1.0 / float(self.N * self.H * self.W), self.loss_kind,
+                                    None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,
+                                    self.loss_alpha, None, None, None, None, self.cpad, self.loss_partials.data_ptr(),
+                                    ctypes.byref(rows), self.N, zt.H, zt.W, self.C, self.H, self.W, st)
         L.reduce_rows(self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0, st)
         if counts is not None:
             L.fill(counts.data_ptr(), 0.0, counts.numel(), st)
-            L.class_counts(self.tptr(zt), zt.ld, self.labels.data_ptr(), counts.data_ptr(), self.N, zt.H, zt.W, self.C,
+            (L.nearest_class_counts if self.nearest_head else L.class_counts)(self.tptr(zt), zt.ld, self.labels.data_ptr(), counts.data_ptr(), self.N, zt.H, zt.W, self.C,
                            self.H, self.W, st)
         return self.loss
 

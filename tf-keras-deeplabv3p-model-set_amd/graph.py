@@ -294,13 +294,17 @@ class GraphBuilder:
             y.channels = filters
         return y if activation is None else self.activation(y, activation, layer=layer)
 
-    def separable_conv2d(self, x, filters, name, activation=None, out=None, pad_to=None):
+    def separable_conv2d(self, x, filters, name, activation=None, out=None, pad_to=None, stride=1, rate=1, l2=0.0):
         """SeparableConv2D(filters, 3, padding='same') (reference unet/models/unet.py:97-138): ONE Keras layer with three weights,
         depthwise_kernel (3,3,Cin,1), pointwise_kernel (1,1,Cin,filters), bias -- a 3x3 depthwise conv and a 1x1 conv with
         no bias and no activation between them.  Plain Keras layer: no regulariser.  Both kernels keep Keras' default
-        glorot_uniform (the layer's kernel_initializer argument reaches neither; DESIGN 4l, unpinned)."""
-        H, W, c = x.shape
+        glorot_uniform (the layer's kernel_initializer argument reaches neither; DESIGN 4l, unpinned).
+        stride / rate: of the depthwise half (DeeplabSeparableConv2D, fast_scnn.py:24,117).  l2: DeeplabSeparableConv2D's
+        kernel_regularizer / bias_regularizer -- Keras' SeparableConv2D hands kernel_regularizer to neither of its two kernels
+        (they have depthwise_regularizer / pointwise_regularizer of their own), so only the bias carries it (unpinned)."""
+        Hi, Wi, c = x.shape
         ck = x.logical_c
+        H, W, pt, pl = conv_geometry(Hi, Wi, 3, stride, rate, 'same')
         layer = self.add_layer(name, 'SeparableConv2D', (H, W, filters), inbound=[x])
         name = layer.name
         cdev = pad_to or filters
@@ -308,10 +312,10 @@ class GraphBuilder:
                               l2=0.0, dev_shape=(3, 3, c, 1))
         pwp = layer.add_param('pointwise_kernel', (1, 1, ck, filters), lambda s: glorot_uniform(self.rng, s, ck, filters),
                               l2=0.0, dev_shape=(1, 1, c, cdev))
-        bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=0.0, dev_shape=(cdev,))
+        bp = layer.add_param('bias', (filters,), lambda s: np.zeros(s, np.float32), l2=l2, dev_shape=(cdev,))
         mid = self.new_tensor(H, W, c, name + '_depthwise')
-        self.ops.append(Op('conv_dw', name=name + '_depthwise', layer=layer, x=x, w=dwp, out=mid, k=3, stride=1, rate=1,
-                           pad_t=1, pad_l=1, Ho=H, Wo=W, c=c, bn=None))
+        self.ops.append(Op('conv_dw', name=name + '_depthwise', layer=layer, x=x, w=dwp, out=mid, k=3, stride=stride, rate=rate,
+                           pad_t=pt, pad_l=pl, Ho=H, Wo=W, c=c, bn=None))
         if out is None:
             out = self.new_tensor(H, W, cdev, name)
         assert (out.H, out.W, out.C) == (H, W, cdev), (name, (out.H, out.W, out.C), (H, W, cdev))
@@ -350,9 +354,10 @@ class GraphBuilder:
         y.channels = x.logical_c
         return y
 
-    def dwconv2d(self, x, k, name, stride=1, rate=1, padding='same', out=None):
+    def dwconv2d(self, x, k, name, stride=1, rate=1, padding='same', out=None, use_bias=False):
         """DeeplabDepthwiseConv2D (reference layers.py:24-31); its kernel_regularizer never reaches the
-        depthwise kernel in Keras -> no l2"""
+        depthwise kernel in Keras -> no l2.  use_bias: Keras' default bias (fast_scnn.py:44), l2 on it; the
+        layer must feed a BatchNormalization, which carries the bias (z stays raw: batchnorm() adds the 'bn_bias' op)"""
         H, W, c = x.shape
         src = x
         if not isinstance(padding, str):
@@ -363,20 +368,26 @@ class GraphBuilder:
                              lambda s: glorot_uniform(self.rng, s, k * k * c, k * k * 1), l2=0.0)
         if out is None:
             out = self.new_tensor(Ho, Wo, c, name)
-        self.ops.append(Op('conv_dw', name=name, layer=layer, x=x, w=wp, out=out, k=k, stride=stride, rate=rate,
-                           pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo, c=c, bn=None))
+        op = Op('conv_dw', name=name, layer=layer, x=x, w=wp, out=out, k=k, stride=stride, rate=rate,
+                pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo, c=c, bn=None)
+        if use_bias:
+            op.dw_bias = layer.add_param('bias', (c,), lambda s: np.zeros(s, np.float32), l2=L2_FACTOR)
+        self.ops.append(op)
         return Value(out, klayer=layer)
 
-    def batchnorm(self, z, name, eps=1e-3, momentum=0.99, group=None, goff=0):
-        """CustomBatchNormalization (reference layers.py:63-70)"""
+    def batchnorm(self, z, name, eps=1e-3, momentum=0.99, group=None, goff=0, channels=None):
+        """CustomBatchNormalization (reference layers.py:63-70).  The producer of z emits the statistics: a conv, or the fused
+        nearest-upsample Add (upsample_add).  channels: the Keras width when z carries zero pad channels behind it (the class
+        logits); the pad entries of the four vectors are zeros on the device, so the pad channels stay exactly 0"""
         assert z.is_plain, 'BatchNormalization expects a raw conv output'
         t = z.tensor
-        layer = self.add_layer(name, 'BatchNormalization', (t.H, t.W, t.C), inbound=[z])
+        layer = self.add_layer(name, 'BatchNormalization', (t.H, t.W, channels or t.C), inbound=[z])
         c = t.C
-        layer.add_param('gamma', (c,), lambda s: np.ones(s, np.float32))
-        layer.add_param('beta', (c,), lambda s: np.zeros(s, np.float32))
-        layer.add_param('moving_mean', (c,), lambda s: np.zeros(s, np.float32), trainable=False)
-        layer.add_param('moving_variance', (c,), lambda s: np.ones(s, np.float32), trainable=False)
+        ck = channels or c
+        layer.add_param('gamma', (ck,), lambda s: np.ones(s, np.float32), dev_shape=(c,))
+        layer.add_param('beta', (ck,), lambda s: np.zeros(s, np.float32), dev_shape=(c,))
+        layer.add_param('moving_mean', (ck,), lambda s: np.zeros(s, np.float32), trainable=False, dev_shape=(c,))
+        layer.add_param('moving_variance', (ck,), lambda s: np.ones(s, np.float32), trainable=False, dev_shape=(c,))
         if group is None:
             group, goff = self.new_group(c), 0
         for i in range(goff, goff + c):
@@ -389,7 +400,12 @@ class GraphBuilder:
         assert prod is not None and prod.bn is None, name
         prod.bn = bn
         self.ops.append(Op('bn', name=name, layer=layer, bn=bn, z=t, producer=prod))
-        return Value(t, group, goff, ACT_NONE, bn, klayer=layer)
+        if getattr(prod, 'dw_bias', None) is not None:
+            self.ops.append(Op('bn_bias', name=layer.name + '_bias', bn=bn, bias=prod.dw_bias))
+        y = Value(t, group, goff, ACT_NONE, bn, klayer=layer)
+        if channels:
+            y.channels = channels
+        return y
 
     def producer_of(self, t):
         for op in reversed(self.ops):
@@ -495,6 +511,28 @@ class GraphBuilder:
             out = self.new_tensor(Ho, Wo, C, layer.name)
         assert (out.H, out.W, out.C) == (Ho, Wo, C), (layer.name, (out.H, out.W, out.C), (Ho, Wo, C))
         self.ops.append(Op('avgpool', name=layer.name, x=v, out=out, k=k, stride=stride, Ho=Ho, Wo=Wo))
+        return Value(out, klayer=layer)
+
+    def winpool2d(self, v, kh, kw, name=None):
+        """AveragePooling2D(pool_size=(kh, kw), strides=(kh, kw)) (reference fast_scnn.py:76): non-overlapping, possibly rectangular
+        windows, floor-sized output (csrc/nearest.hip)"""
+        H, W, C = v.shape
+        Ho, Wo = H // kh, W // kw
+        layer = self.add_layer(name, 'AveragePooling2D', (Ho, Wo, C), inbound=[v])
+        out = self.new_tensor(Ho, Wo, C, layer.name)
+        self.ops.append(Op('winpool', name=layer.name, x=v, out=out, kh=kh, kw=kw, Ho=Ho, Wo=Wo))
+        return Value(out, klayer=layer)
+
+    def upsample_add(self, a, b, factor, name=None):
+        """Add([a, UpSampling2D((factor, factor))(b)]) with b left at its own resolution: one fused launch that also emits the
+        statistics of a BatchNormalization that follows (batchnorm() finds this op as the producer).  `b` is the Keras tensor that
+        the reference computes at a's resolution from an upsampled input; every layer between the UpSampling2D and the Add
+        commutes with it"""
+        H, W, C = a.shape
+        assert (b.tensor.H * factor, b.tensor.W * factor, b.tensor.C) == (H, W, C), (a.shape, b.shape, factor)
+        layer = self.add_layer(name, 'Add', (H, W, C), inbound=[a, b])
+        out = self.new_tensor(H, W, C, layer.name)
+        self.ops.append(Op('up_add', name=layer.name, x=a, r=b, out=out, factor=factor, bn=None))
         return Value(out, klayer=layer)
 
     def global_avgpool(self, v, name=None, kind='AveragePooling2D'):

@@ -1060,7 +1060,8 @@ DeeplabModel.evaluate_miou = _evaluate_miou
 # GEMM) and max pooling (dl3p_maxpool2d_*_bf16) closed the gap for Xception and ResNet50 -- train.py:37-46 applies the policy to
 # every model type.  The U-Net types (get_unet_model) are refused under the policy whether built for training or not: the 2x2
 # stride-2 transposed conv (csrc/deconv.hip) has no bf16 twin yet.
-_NO_BF16_TRAINING = {'unet_standard': 'dl3p_deconv2x2_* has no bf16 kernels', 'unet_lite': 'dl3p_deconv2x2_* has no bf16 kernels'}
+_NO_BF16_TRAINING = {'unet_standard': 'dl3p_deconv2x2_* has no bf16 kernels', 'unet_lite': 'dl3p_deconv2x2_* has no bf16 kernels',
+                     'fast_scnn': 'the nearest-upsampling and window-pooling kernels have no bf16 twins'}
 
 
 def get_deeplabv3p_model(model_type, num_classes, model_input_shape, output_stride, freeze_level=0,
@@ -1178,6 +1179,46 @@ def get_unet_model(model_type, num_classes, model_input_shape, freeze_level=0, w
         raise AssertionError('head tensor layout')
     model = DeeplabModel(g, x, model_type, num_classes, (H, W), training, base_len, seed=seed, bf16=False)
     model.name = model_type
+    if weights_path:
+        model.load_weights(weights_path, by_name=False)
+        print('Load weights {}.'.format(weights_path))
+    return model
+
+
+def get_fast_scnn_model(model_type, num_classes, model_input_shape, weights_path=None, training=True, seed=0,
+                        bn_moving_variance='biased'):
+    """fast_scnn/model.py:19-45, same positional arguments (+ `seed` and `bn_moving_variance`, as get_deeplabv3p_model has them):
+    'fast_scnn' with the reference's own head -- Dropout(0.3) -> UpSampling2D((8, 8)) -> [Reshape] -> Softmax('pred_mask') -- served
+    by the nearest head kernels from the logits at H/8.  The returned model is a DeeplabModel like every other family's."""
+    from . import mixed_precision, fast_scnn as fs_mod
+    if model_type not in fs_mod.fast_scnn_model_map.keys():
+        raise ValueError('This model type is not supported now')
+    if not 1 <= int(num_classes) <= 253:
+        raise ValueError('num_classes must be in [1, 253] (got %r)' % (num_classes,))
+    if bn_moving_variance not in ('biased', 'unbiased'):
+        raise ValueError("bn_moving_variance must be 'biased' or 'unbiased' (got %r)" % (bn_moving_variance,))
+    H, W = model_input_shape
+    if H % 32 or W % 32 or H < 256 or W < 256:
+        # five stride-2 stages, then pool_size = ((H / 32) // 8, (W / 32) // 8) in the pyramid pooling block: 0 below 256, and Keras
+        # cannot build AveragePooling2D(pool_size=0)
+        raise ValueError('Fast-SCNN input height and width must be multiples of 32 and at least 256: the pyramid pooling block '
+                         'pools with pool_size = (H/32)//8, which Keras cannot build for smaller inputs (got %r)' % ((H, W),))
+    if mixed_precision.is_bf16() and model_type in _NO_BF16_TRAINING:
+        raise ValueError("model type '%s' is not built for the mixed_bfloat16 policy (%s); build it under the float32 policy"
+                         % (model_type, _NO_BF16_TRAINING[model_type]))
+    g, x = fs_mod.fast_scnn_model_map[model_type](num_classes, input_shape=(H, W, 3), weights=None, training=training, seed=seed)
+    base_len = len(g.layers)
+    out = g.passthrough(x, 'UpSampling2D', (H, W, num_classes), name='up_sampling2d_1')
+    if training:
+        out = g.passthrough(out, 'Reshape', (H * W, num_classes), name='reshape')
+    out = g.passthrough(out, 'Softmax', (H * W, num_classes) if training else (H, W, num_classes), name='pred_mask')
+    g.output_layer = out.klayer
+    cpad = (num_classes + g.align - 1) // g.align * g.align
+    if x.tensor.C != cpad or not x.is_plain or (x.tensor.H * 8, x.tensor.W * 8) != (H, W):
+        raise AssertionError('head tensor layout')
+    model = DeeplabModel(g, x, model_type, num_classes, (H, W), training, base_len, seed=seed, bf16=False)
+    model.name = 'Fast_SCNN'
+    model.graph.bn_moving_variance = model.bn_moving_variance = bn_moving_variance
     if weights_path:
         model.load_weights(weights_path, by_name=False)
         print('Load weights {}.'.format(weights_path))

@@ -1310,3 +1310,106 @@ def deconv2x2_bwd_weight(x, dy, in_scale=None, in_shift=None, in_act=ACT_NONE, w
     lib().deconv2x2_bwd_weight(xp, ldx, _p(in_scale), _p(in_shift), in_act, dp, ldd, _p(gw), _p(gb), _p(ws),
                                ws.numel() * 4, N, H, W, Cin, Cout, _stream())
     return (gw, gb) if with_bias else gw
+
+
+# ------------------------------------------------------------------------------------- nearest upsampling (Fast-SCNN)
+def upsample_add_fwd(a, b, r, a_scale=None, a_shift=None, a_act=ACT_NONE, b_scale=None, b_shift=None, b_act=ACT_NONE, out=None,
+                     partials=None):
+    """a (N,r h,r w,C) + UpSampling2D(r)(b), b (N,h,w,C), each behind its own prologue -> out [, rows of `partials` written: the
+    sum / sum of squares of `out` for the BatchNorm that follows]"""
+    N, H, W, C = a.shape
+    h, w = b.shape[1], b.shape[2]
+    y = out if out is not None else torch.empty((N, H, W, C), dtype=torch.float32, device=a.device)
+    ap, lda = _pl(a)
+    bp, ldb = _pl(b)
+    yp, ldy = _pl(y)
+    rows = ctypes.c_int(0)
+    lib().upsample_add_fwd(ap, lda, _p(a_scale), _p(a_shift), a_act, bp, ldb, _p(b_scale), _p(b_shift), b_act, yp, ldy,
+                           _p(partials), ctypes.byref(rows), N, h, w, C, H, W, r, _stream())
+    return (y, rows.value) if partials is not None else y
+
+
+def block_sum_bwd(g, r, out=None, accumulate=False):
+    """g (N,r h,r w,C) -> (N,h,w,C): the sum over every r x r block (the transpose of UpSampling2D(r)); `out` (+)= it"""
+    N, H, W, C = g.shape
+    h, w = (out.shape[1], out.shape[2]) if out is not None else (H // r, W // r)
+    gl = out if out is not None else torch.empty((N, h, w, C), dtype=torch.float32, device=g.device)
+    gp, ldg = _pl(g)
+    lp, ldl = _pl(gl)
+    lib().block_sum_bwd(gp, ldg, lp, ldl, int(accumulate), N, h, w, C, H, W, r, _stream())
+    return gl
+
+
+def winpool2d_fwd(x, kh, kw, in_scale=None, in_shift=None, in_act=ACT_NONE, out=None):
+    """x (N,H,W,C) -> AveragePooling2D((kh,kw), strides=(kh,kw), 'valid'): (N, H // kh, W // kw, C); `out` may be a channel slice"""
+    N, H, W, C = x.shape
+    Ho, Wo = H // kh, W // kw
+    y = out if out is not None else torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    xp, ldx = _pl(x)
+    yp, ldy = _pl(y)
+    lib().winpool2d_fwd(xp, ldx, _p(in_scale), _p(in_shift), in_act, yp, ldy, N, H, W, C, kh, kw, Ho, Wo, _stream())
+    return y
+
+
+def winpool2d_bwd(dy, x_shape, kh, kw, out=None, accumulate=False):
+    """d/d(activated input) of winpool2d_fwd; `out` (+)= it, uncovered rows and columns get 0"""
+    N, H, W, C = x_shape
+    gx = out if out is not None else torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    dp, ldd = _pl(dy)
+    gp, ldg = _pl(gx)
+    lib().winpool2d_bwd(dp, ldd, gp, ldg, int(accumulate), N, H, W, C, kh, kw, dy.shape[1], dy.shape[2], _stream())
+    return gx
+
+
+def nearest_softmax_probs(z, C, H, W):
+    """z (N,h,w,Cpad) logits -> Softmax(UpSampling2D(H / h)(z)) as (N,H,W,C): one softmax per logit pixel"""
+    N, h, w, _ = z.shape
+    zp, ldz = _pl(z)
+    probs = torch.empty((N, H, W, C), dtype=torch.float32, device=z.device)
+    lib().nearest_softmax_probs(zp, ldz, _p(probs), N, h, w, C, H, W, _stream())
+    return probs
+
+
+def nearest_head_train(z, C, H, W, labels, ignore_index=255, loss=('ce',), pixel_weights=None, want_grad=True, out=None,
+                       accumulate=False):
+    """training head behind a nearest upsampling: z (N,h,w,Cpad), labels [N*H*W] -> (loss [1], d loss / d z (N,h,w,Cpad) or None);
+    loss: ('ce',) | ('weighted', weight tensor [C]) | ('focal', gamma, alpha), as upsample_softmax_ce"""
+    N, h, w, cp = z.shape
+    dev = z.device
+    zp, ldz = _pl(z)
+    gz = out
+    if want_grad and gz is None:
+        gz = torch.zeros((N, h, w, cp), dtype=torch.float32, device=dev)
+    gp, ldg = _pl(gz if want_grad else None)
+    partial = torch.zeros(MAX_STAT_ROWS, dtype=torch.float32, device=dev)
+    rows = ctypes.c_int(0)
+    kind = {'ce': 0, 'weighted': 1, 'focal': 2}[loss[0]]
+    cw = loss[1] if kind == 1 else None
+    gamma, alpha = (float(loss[1]), float(loss[2])) if kind == 2 else (0.0, 0.0)
+    lib().nearest_head_train(zp, ldz, _p(labels), int(ignore_index or 0), 1.0 / float(N * H * W), kind, _p(cw), gamma, alpha,
+                             _p(pixel_weights), gp, ldg, int(accumulate), _p(partial), ctypes.byref(rows), N, h, w, C, H, W,
+                             _stream())
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    lib().reduce_rows(_p(partial), rows.value, 1, _p(total), 0, _stream())
+    return total, (gz if want_grad else None)
+
+
+def nearest_argmax_confusion(z, C, H, W, labels=None, confusion=None, want_mask=False):
+    """argmax_confusion behind a nearest upsampling: (pred mask (N,H,W) int32 or None, confusion (C,C) int64 or None)"""
+    N, h, w, _ = z.shape
+    zp, ldz = _pl(z)
+    pred = torch.empty((N, H, W), dtype=torch.int32, device=z.device) if want_mask else None
+    if labels is not None and confusion is None:
+        confusion = torch.zeros((C, C), dtype=torch.int64, device=z.device)
+    lib().nearest_argmax_confusion(zp, ldz, _p(labels), _p(pred), _p(confusion) if labels is not None else None, N, h, w, C, H,
+                                   W, _stream())
+    return pred, (confusion if labels is not None else None)
+
+
+def nearest_class_counts(z, C, H, W, labels):
+    """-> counts (N,3,C) int32: |label == c and pred == c|, |label == c|, |pred == c| per image (dl3p_class_counts)"""
+    N, h, w, _ = z.shape
+    zp, ldz = _pl(z)
+    counts = torch.zeros((N, 3, C), dtype=torch.int32, device=z.device)
+    lib().nearest_class_counts(zp, ldz, _p(labels), _p(counts), N, h, w, C, H, W, _stream())
+    return counts
