@@ -622,7 +622,9 @@ int dl3p_pwconv_bwd_weight_slabs_bn(const float* x, int ldx, const float* in_sca
                                     int* rows_out, int M, int K, int N, void* stream);
 /* Decoder_block (deeplabv3p/models/layers.py:207-215: x = img_resize(x) -> Concatenate([x, skip]) -> SepConv_BN) without the resized
  * tensor in HBM.  dl3p_dw_upsampled_input describes the input of the NEXT dl3p_dwconv2d_fwd / dl3p_dwconv2d_bwd_weight_slabs /
- * dl3p_dwconv2d_bwd_weight_slabs_bn call of the calling thread (one call consumes it): channels [0, up_C) of x are not read but
+ * dl3p_dwconv2d_bwd_weight_slabs_bn call of the calling thread (also dl3p_dwconv2d_bwd_weight).  That call consumes it on entry,
+ * before any of its argument checks, so a call that fails has consumed it too and never leaves it armed for a later one; the
+ * _supported functions and dl3p_dw_plan_query do not touch it.  Channels [0, up_C) of x are not read but
  * formed on the fly as the bilinear upsampling of up_x (N, up_h, up_w, up_C; row pitch up_ld) to the conv's H x W, with
  * dl3p_resize_bilinear_fwd's arithmetic expression for expression -- the output equals resize + conv bit for bit; channels from up_C
  * on are read from x as ever.  Served: 3x3, stride 1, rate 1 launches of the window kernels behind a BatchNorm + activation

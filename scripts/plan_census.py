@@ -13,6 +13,7 @@ A knob's environment variable is read once per process, so every environment sta
 always set explicitly.  The default state is written in full, one line per shape; every other state lists the lines that
 differ from its base.  --quick: a thinned shape and state list (tests/test_plan_census_cpu.py).
 """
+import ast
 import ctypes
 import json
 import os
@@ -84,9 +85,24 @@ def shapes(quick):
     return sorted(s for s in out if s[0] > 0)
 
 
+def edge_cases():
+    """the geometries of the depthwise edge suite (CASES of tests/test_dw_edges_gpu.py, read from its source): gather, residue-class,
+    5x5 and narrow-map plans next to the tuned production shapes.  -> (N, H, W, C, k, stride, rate, pad); pad: None = TF SAME"""
+    tree = ast.parse(open(os.path.join(ROOT, 'tests', 'test_dw_edges_gpu.py')).read())
+    table = next(n.value for n in tree.body if isinstance(n, ast.Assign) and getattr(n.targets[0], 'id', '') == 'CASES')
+    out = []
+    for call in table.elts:
+        kw = {k.arg: ast.literal_eval(k.value) for k in call.keywords}
+        pad = kw.get('pad', 'same')
+        out.append(tuple(ast.literal_eval(a) for a in call.args[1:5]) + (kw.get('k', 3), kw.get('s', 1), kw.get('r', 1),
+                                                                         None if pad == 'same' else tuple(pad)))
+    return out
+
+
 def dw_keys(quick):
-    keys = sorted({r[1:8] for r in table_rows('dw_tuned.h', 12)})
-    return keys[::5] if quick else keys
+    keys = sorted({r[1:8] + (None,) for r in table_rows('dw_tuned.h', 12)})
+    edges = [c for c in dict.fromkeys(edge_cases()) if c not in keys]
+    return (keys[::5] if quick else keys) + edges          # (the edge geometries are few and each is there for a reason: never thinned)
 
 
 def load(path):
@@ -99,14 +115,19 @@ def load(path):
                             ('dl3p_pwconv_bwd_weight_workspace', ctypes.c_size_t, [i] * 3),
                             ('dl3p_conv2d_gemm_bwd_weight_workspace', ctypes.c_size_t, [i] * 6),
                             ('dl3p_pwconv_fwd_splitk_plan', i, [i] * 3), ('dl3p_pwconv_fwd_splitk_workspace', ctypes.c_size_t, [i] * 3),
-                            ('dl3p_pwconv_bwd_data_sb_apply_supported', i, [i] * 5), ('dl3p_pwconv_bwd_weight_bn_supported', i, [i] * 3)):
+                            ('dl3p_pwconv_bwd_data_sb_apply_supported', i, [i] * 5), ('dl3p_pwconv_bwd_weight_bn_supported', i, [i] * 3),
+                            ('dl3p_dwconv2d_bwd_weight_bn_supported', i, [i] * 11), ('dl3p_dw_upsampled_input_supported', i, [i] * 13),
+                            ('dl3p_dwconv2d_bwd_weight_workspace', ctypes.c_size_t, [i] * 5)):
         f = getattr(L, name)
         f.restype, f.argtypes = res, args
     return L
 
 
-def same_geometry(H, W, k, stride, rate):
+def geometry(H, W, k, stride, rate, pad):
+    """Ho, Wo, pad_t, pad_l; pad: None = TF SAME, or (top, bottom, left, right)"""
     keff = k + (k - 1) * (rate - 1)
+    if pad:
+        return (H + pad[0] + pad[1] - keff) // stride + 1, (W + pad[2] + pad[3] - keff) // stride + 1, pad[0], pad[2]
     Ho, Wo = -(-H // stride), -(-W // stride)
     return Ho, Wo, max((Ho - 1) * stride + keff - H, 0) // 2, max((Wo - 1) * stride + keff - W, 0) // 2
 
@@ -131,12 +152,16 @@ def census(L, shape_list, dw_list):
         f.append('apply=' + ''.join('%d' % L.dl3p_pwconv_bwd_data_sb_apply_supported(M, K, N, act, s) for act in range(4) for s in (0, 1)))
         f.append('wbn=%d' % L.dl3p_pwconv_bwd_weight_bn_supported(M, K, N))
         lines.append(' '.join(f))
-    for N, H, W, C, k, stride, rate in dw_list:
-        Ho, Wo, pt, pl = same_geometry(H, W, k, stride, rate)
-        f = ['dw %d %d %d %d %d %d %d' % (N, H, W, C, k, stride, rate)]
+    for N, H, W, C, k, stride, rate, pad in dw_list:
+        Ho, Wo, pt, pl = geometry(H, W, k, stride, rate, pad)
+        f = ['dw %d %d %d %d %d %d %d%s' % (N, H, W, C, k, stride, rate, ' pad=%d,%d,%d,%d' % pad if pad else '')]
         for role in range(4):
             rc = L.dl3p_dw_plan_query(role, N, H, W, C, k, stride, rate, pt, pl, Ho, Wo, out6)
             f.append('q%d=%s' % (role, ','.join(str(v) for v in out6) if rc == 0 else 'rc%d' % rc))
+        f.append('wbn=%d' % L.dl3p_dwconv2d_bwd_weight_bn_supported(N, H, W, C, k, stride, rate, pt, pl, Ho, Wo))
+        f.append('up=' + ''.join('%d' % L.dl3p_dw_upsampled_input_supported(r, N, H, W, C, 4, k, stride, rate, pt, pl, Ho, Wo)
+                                 for r in (0, 1)))
+        f.append('ws=%d' % L.dl3p_dwconv2d_bwd_weight_workspace(N, Ho, Wo, C, k))
         lines.append(' '.join(f))
     lines.append('get_option ' + ' '.join('%s=%d' % (n, L.dl3p_get_option(n.encode())) for n in GET_NAMES + ('no_such_knob',)))
     return lines

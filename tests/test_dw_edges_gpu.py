@@ -208,8 +208,9 @@ def reported(L, c):
     return (f, d, w, up[0], up[1], fold)
 
 
-# ---- which kernel instantiation a launch is (launch_fwd_pro / launch_bwdw / launch_bwdw_bna / the data-gradient entries of
-# csrc/dwconv.hip restated over the plan query); env: the DL3P_* switches of the process
+# ---- which kernel instantiation a launch is (the launch switches of csrc/dwconv.hip -- launch_fwd / launch_fwd_pro for a planned
+# forward or flipped problem, launch_bwdw / launch_bwdw_bna behind dw_plan_wgrad, the data-gradient entries' own stride > 1 launches
+# -- restated over the plan query); env: the DL3P_* switches of the process
 def _pro_of(sc, act):
     return 2 if act != NONE else (1 if sc else 0)
 
@@ -1060,7 +1061,7 @@ def test_upsampled_input(ops, c):
         if not WANT[c.name][3]:
             with pytest.raises(ops.Dl3pError):
                 run_forward(L, c, inp, 'relu6', 'view', up=(upx, up_C))
-            continue          # (the armed description was consumed by the refused call: dw_take_up runs before the check)
+            continue          # (the armed description was consumed by the refused call: dw_take_up is the entry's first action)
         for pname in ('relu6', 'hswish'):
             run_forward(L, c, inp, pname, 'view', up=(upx, up_C))
         run_wgrad(L, c, inp, 'relu6', 'view', up=(upx, up_C))

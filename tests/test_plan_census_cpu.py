@@ -23,7 +23,10 @@ def test_plan_census_runs_twice_alike_and_restores_every_option(tmp_path):
     assert defaults.startswith('== defaults\n')
     shape_lines = [l for l in defaults.split('\n') if re.match(r'^\d+ \d+ \d+ q0=', l)]
     assert len(shape_lines) > 100 and all(' q9=' in l and ' ws=' in l and ' wbn=' in l for l in shape_lines)
-    assert any(l.startswith('dw ') for l in defaults.split('\n'))
+    dw_lines = [l for l in defaults.split('\n') if l.startswith('dw ')]
+    assert dw_lines and all(' q3=' in l and ' wbn=' in l and re.search(r' up=[01]{2} ws=\d+$', l) for l in dw_lines)
+    # the geometries of the depthwise edge suite are in: explicit paddings, a residue-class plan (kind 3), a gather (kind 0)
+    assert any(' pad=' in l for l in dw_lines) and any(' q0=3,' in l for l in dw_lines) and any(' q0=0,' in l for l in dw_lines)
     got = re.search(r'^get_option (.*)$', defaults, re.M).group(1)
     assert re.fullmatch(r'split_wgrad=-?\d+ conv_sb=-?\d+ sb_rs=-?\d+ sb3=-?\d+ sb_pipe=-?\d+ splitk=-?\d+ no_such_knob=-2147483648', got), got
     # every option the tool moved: accepted, some value of it changes an answer or none does, and after its restore value EVERY

@@ -73,6 +73,45 @@ def test_unserved_geometries_are_refused(ops):
     assert torch.equal(ops.dwconv2d_fwd(x, w), torch.zeros_like(x))   # (the failed call consumed the description)
 
 
+@pytest.mark.parametrize('entry', ['fwd', 'bwd_weight', 'bwd_weight_slabs_bn'])
+def test_a_call_refused_at_its_first_check_leaves_nothing_armed(ops, entry):
+    """The consuming entry points take the armed description before any check that can return: a call refused for its kernel size
+    (check_dw_common, the first check) has consumed it, and the next plain call -- one the UP form WOULD serve: 3x3 stride 1 window
+    kernel behind BatchNorm + ReLU -- reads its whole input from x, bit for bit as before."""
+    N, H, W, C, C1 = 1, 8, 8, 8, 4
+    g = torch.Generator(device=DEV); g.manual_seed(5)
+    rnd = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    low, x, dy, wk = rnd(N, 3, 3, C1).abs(), rnd(N, H, W, C), rnd(N, H, W, C), rnd(3, 3, C) * 0.3
+    sc, sh = torch.rand(C, device=DEV, generator=g) + 0.5, rnd(C) * 0.3
+    pro = dict(in_scale=sc, in_shift=sh, in_act=ops.ACT_RELU)
+    L = ops.lib()
+    geo = (N, H, W, C, C1, 3, 1, 1, 1, 1, H, W)
+    assert L.dw_upsampled_input_supported(0, *geo) == 1 and L.dw_upsampled_input_supported(1, *geo) == 1
+    bn = ops.BNState(C, DEV)
+    bn.scale.copy_(torch.rand(C, device=DEV, generator=g) + 0.5); bn.shift.copy_(rnd(C) * 0.2)
+    bn.mean.copy_(rnd(C) * 0.1); bn.invstd.copy_(torch.rand(C, device=DEV, generator=g) + 0.5)
+    bn.coef.copy_(torch.cat([bn.scale, rnd(C) * 0.01, rnd(C) * 0.01]))
+    z = rnd(N, H, W, C)
+
+    def call(k, **kw):
+        """-> the tensors the entry writes, the statistic rows of the forward included"""
+        if entry == 'fwd':
+            part = ops.new_partials(C, DEV)
+            y, rows = ops.dwconv2d_fwd(x, rnd(k, k, C) if k != 3 else wk, partials=part, **pro, **kw)
+            return y, part[:rows * 2 * C].clone()
+        if entry == 'bwd_weight':
+            return (ops.dwconv2d_bwd_weight(x, dy, k, **pro, **kw),)
+        return ops.dwconv2d_bwd_weight_bn(x, dy, z, bn, ops.ACT_RELU, k, **pro, **kw)
+    before = call(3)
+    with pytest.raises(ops.Dl3pError):
+        call(4, upsampled=low)
+    after = call(3)
+    assert len(before) == len(after) and all(torch.equal(a, b) for a, b in zip(before, after))
+    # (and the armed form itself is another result: the check above can tell a stale description from none)
+    armed = call(3, upsampled=low)
+    assert not torch.equal(armed[0], before[0])
+
+
 @pytest.mark.parametrize('model_type,H,W,N', [('mobilenetv2', 129, 129, 2), ('xception', 65, 97, 2), ('mobilenetv2', 513, 513, 2)])
 def test_the_step_with_the_resize_folded_is_the_unfolded_step_bit_for_bit(model_type, H, W, N, monkeypatch):
     C = 21

@@ -1318,10 +1318,6 @@ static int pick_band(long long items_per_row_band, int rows, int px, int nslab) 
   return th;
 }
 
-// variant + work decomposition of a forward depthwise launch
-//   kind 1: window kernel TW=4, stride 1 (any rate, on the rate x rate sub-lattices)
-//   kind 2: window kernel TW=2, stride 2, rate 1
-//   kind 0: per-pixel gather (stride > 1 with rate > 1, or maps narrower than a strip)
 // strip width of the 5x5 stride-1 rolling-row kernel: 4 columns per thread on the narrow maps (33 wide and the 17-wide
 // sub-lattices of rate 2: 37 vs 55 us at 33x33x672), 2 on the wide ones (65x65x120: 49 vs 58 us, the bands stay taller).
 // DL3P_DW5_ROWS = 2 | 4 forces one, 0 selects the older register-window kernel (1 wave per SIMD, kept for comparison).
@@ -1332,28 +1328,95 @@ static int dw5_rows_tw(int uw) {
 }
 static int dw5_tw(int uw) { return dw5_rows_tw(uw) == 4 ? 4 : 2; }
 
+// what a launch computes: the numbers dw_tuned.h and dl3p_dw_plan_query give the four roles
+enum DwRole { DW_FWD = 0, DW_DGRAD = 1, DW_DGRAD_BN = 2, DW_WGRAD = 3 };
+
 // Measured plan choices of the window kernels for the depthwise shapes of the BASELINE graphs (scripts/tune_dw.py writes
 // dw_tuned.h): role 0 forward, 1 data gradient, 2 data gradient + fused BatchNorm sums, 3 weight gradient; the key is the
 // geometry the planner sees (for the data gradient that is the flipped problem: H x W of dy).  per_cu: persistent
 // workgroups per CU; want: workgroup-iterations the row-band split aims for; maxth: tallest band.  0 = keep the default.
 struct DwTuned { int role, N, H, W, C, k, stride, rate, per_cu, want, maxth, tw; };   // tw: strip width of the 3x3 stride-1 window kernels (0 / 4, or 2)
 #include "dw_tuned.h"
-static const DwTuned* dw_tuned_lookup(const DwParams& p) {
+static const DwTuned* dw_tuned_lookup(const DwParams& p, DwRole role) {
   if (!opt(OPT_DW_TUNED)) return nullptr;
-  const int role = p.bb_z ? 2 : (p.flip ? 1 : (p.dy ? 3 : 0));
   for (size_t i = 0; i < sizeof(g_dw_tuned) / sizeof(g_dw_tuned[0]); ++i) {
     const DwTuned& e = g_dw_tuned[i];
-    if (e.role == role && e.N == p.N && e.H == p.H && e.W == p.W && e.C == p.C && e.k == (p.ks5 ? 5 : 3) && e.stride == p.stride &&
+    if (e.role == role && e.N == p.N && e.H == p.H && e.W == p.W && e.C == p.C && e.k == p.ks && e.stride == p.stride &&
         e.rate == p.rate)
       return &e;
   }
   return nullptr;
 }
 
-static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 = 0) {
+// ---- the problems.  A builder fills what follows from the conv's own geometry (extents, padding, channel lanes, ks / ks5);
+// pointers, leading dimensions, prologue and accumulate are set by the caller around it.
+struct DwGeom { int N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo; };   // the conv as every entry point receives it
+
+// the conv as stated: the weight gradient's problem as it is (x (N,H,W,C) against dy (N,Ho,Wo,C)), the base of the other three
+static DwParams dw_conv_problem(const DwGeom& g) {
+  DwParams p = {};
+  p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.Ho = g.Ho; p.Wo = g.Wo; p.stride = g.stride; p.rate = g.rate;
+  p.pad_t = g.pad_t; p.pad_l = g.pad_l;
+  p.ks = g.k; p.ks5 = g.k == 5;
+  pick_lanes(g.C, &p.c4s, &p.px, &p.nslab);
+  return p;
+}
+// forward x (N,H,W,C) -> y (N,Ho,Wo,C).  5x5 keeps its weights in LDS (25 x c4s float4): at most 64 channel lanes per workgroup
+static DwParams dw_forward_problem(const DwGeom& g) {
+  DwParams p = dw_conv_problem(g);
+  if (g.k == 5) {
+    const int c4 = g.C / 4;
+    int best = 1;
+    for (int d = 1; d <= c4 && d <= 64; ++d)
+      if (c4 % d == 0 && (256 / d) * d >= (256 / best) * best) best = d;
+    p.c4s = best; p.px = 256 / best; p.nslab = c4 / best;
+  }
+  return p;
+}
+// data gradient of a STRIDE-1 conv: correlation with the flipped kernel, a forward conv from dy (N,Ho,Wo,C) to gx (N,H,W,C) with
+// pad' = rate*(k-1) - pad
+static DwParams dw_flipped_problem(const DwGeom& g) {
+  DwGeom f = g;
+  f.H = g.Ho; f.W = g.Wo; f.Ho = g.H; f.Wo = g.W; f.stride = 1;
+  f.pad_t = g.rate * (g.k - 1) - g.pad_t; f.pad_l = g.rate * (g.k - 1) - g.pad_l;
+  DwParams p = dw_forward_problem(f);
+  p.flip = 1; p.act = DL3P_ACT_NONE;
+  return p;
+}
+// data gradient at stride > 1, planned here: stride 2 at rate 1 walks 2 x 2 quads of gx (dw_bwd_data_s2), anything else gathers
+// per input pixel (dw_bwd_data_strided)
+static DwParams dw_strided_dgrad_problem(const DwGeom& g) {
+  DwParams p = dw_conv_problem(g);
+  if (g.stride == 2 && g.rate == 1) {
+    p.th = ((g.H - 1 + g.pad_t) >> 1) + 1;     // quads per column
+    p.spr = ((g.W - 1 + g.pad_l) >> 1) + 1;    // quads per row
+    p.total = (long long)g.N * p.th * p.spr;
+  } else {
+    p.total = (long long)g.N * g.H * g.W;
+  }
+  p.nbx = pick_nbx(p.total, p.px, p.nslab);
+  return p;
+}
+
+// ---- the planner: variant + work decomposition of a launch over the forward, flipped or weight-gradient problem
+//   kind 1: window kernel, stride 1 (any rate, on the rate x rate sub-lattices)
+//   kind 2: window kernel, stride 2, rate 1
+//   kind 3: residue-class kernels (p.lat = 2 | 3): 3x3 'same' at a rate that 2 or 3 steps carry across the map
+//   kind 0: per-pixel gather (stride > 1 with rate > 1, or maps narrower than a strip)
+struct DwPlanOpts {
+  int per_cu;          // persistent workgroups per CU, where neither the table nor set_option names one
+  bool window5;        // 5x5 may take a window kernel
+  int tw5;             // strip width of its stride-1 kernel, 0 = dw5_tw's
+};
+static DwPlanOpts dw_forward_opts(int tw5 = 0) {          // roles DW_FWD, DW_DGRAD, DW_DGRAD_BN
+  static const int dwf_per_cu = env_int("DL3P_DWF_PER_CU", 8);
+  return {dwf_per_cu, true, tw5};
+}
+
+static int dw_plan(DwParams& p, DwRole role, const DwPlanOpts& o) {
   int kind = 0;
-  int t_want = 0, t_maxth = 0, t_tw = 0;
-  if (const DwTuned* e = dw_tuned_lookup(p)) {
+  int per_cu = o.per_cu, t_want = 0, t_maxth = 0, t_tw = 0;
+  if (const DwTuned* e = dw_tuned_lookup(p, role)) {
     if (e->per_cu) per_cu = e->per_cu;
     t_want = e->want; t_maxth = e->maxth; t_tw = e->tw;
   }
@@ -1362,18 +1425,21 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
   if (opt_set(OPT_DW_WANT)) t_want = opt_set(OPT_DW_WANT);
   if (opt_set(OPT_DW_MAXTH)) t_maxth = opt_set(OPT_DW_MAXTH);
   // 5x5: window kernels with LDS weights in the forward / data-gradient role (strips of 2 at stride 1, 1 at stride 2);
-  // the weight gradient keeps the per-pixel gather (25 tap accumulators + a 5-row window do not fit)
-  if (p.ks5 && !window5) kind = 0;
+  // the weight gradient has its rolling-row kernel at stride 1 and the per-pixel gather elsewhere (25 tap accumulators + a
+  // 5-row window do not fit)
+  if (p.ks5 && !o.window5) kind = 0;
   else if (p.stride == 1 && ceil_div(p.Wo, p.rate) >= 4) kind = 1;
   else if (p.stride == 2 && p.rate == 1 && p.Wo >= 4) kind = 2;
-  if (kind == 0 && p.ks == 3 && p.stride == 1 && p.pad_t == p.rate && p.pad_l == p.rate && p.Ho == p.H && p.Wo == p.W &&
-      2 * p.rate >= p.H && 2 * p.rate >= p.W && p.rate < p.H && p.rate < p.W &&
-      (long long)p.N * p.H * p.W * (p.ldx > p.ldy ? p.ldx : p.ldy) < (1LL << 31)) { kind = 3; p.lat = 2; }
-  // one step down: 3 * rate covers the map (rate 12 on 33 x 33, rate 36 on 97 x 97) -> 3 x 3 pixels per class
+  // residue classes (there is no weight-gradient kernel of that form): lat * rate covers the map -> lat x lat pixels per class.
+  // 2: the largest ASPP rate; 3, one step down: rate 12 on 33 x 33, rate 36 on 97 x 97
   static const int lat3 = env_int("DL3P_DW_LAT3", 1);
-  if (kind == 0 && lat3 && p.ks == 3 && p.stride == 1 && p.pad_t == p.rate && p.pad_l == p.rate && p.Ho == p.H && p.Wo == p.W &&
-      3 * p.rate >= p.H && 3 * p.rate >= p.W && p.rate < p.H && p.rate < p.W &&
-      (long long)p.N * p.H * p.W * (p.ldx > p.ldy ? p.ldx : p.ldy) < (1LL << 31)) { kind = 3; p.lat = 3; }
+  const auto lattice = [&](int lat) {
+    return kind == 0 && role != DW_WGRAD && p.ks == 3 && p.stride == 1 && p.pad_t == p.rate && p.pad_l == p.rate && p.Ho == p.H &&
+           p.Wo == p.W && lat * p.rate >= p.H && lat * p.rate >= p.W && p.rate < p.H && p.rate < p.W &&
+           (long long)p.N * p.H * p.W * (p.ldx > p.ldy ? p.ldx : p.ldy) < (1LL << 31);
+  };
+  if (lattice(2)) { kind = 3; p.lat = 2; }
+  else if (lat3 && lattice(3)) { kind = 3; p.lat = 3; }
   if (kind == 3) {
     p.spr = p.rate; p.th = 1; p.nbands = p.rate;
     p.total = (long long)p.N * p.rate * p.rate;      // one work item per residue class (py, px)
@@ -1385,7 +1451,7 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
     const int uw = ceil_div(p.Wo, r), uh = ceil_div(p.Ho, r);      // sub-lattice size
     // 3x3 stride 1: strips of 4 outputs (6-column window, 184-240 VGPRs: two waves per SIMD) or of 2 (160-192 VGPRs, three
     // waves per SIMD for the forward and the weight gradient, a third more window loads per output) -- the tuner's call
-    const int TW = p.ks5 ? (kind == 1 ? (tw5 ? tw5 : dw5_tw(uw)) : 1) : (kind == 1 ? (t_tw == 2 ? 2 : 4) : 2);
+    const int TW = p.ks5 ? (kind == 1 ? (o.tw5 ? o.tw5 : dw5_tw(uw)) : 1) : (kind == 1 ? (t_tw == 2 ? 2 : 4) : 2);
     p.tw = TW;
     p.spr = ceil_div(uw, TW);
     // bands of equal height (+-1 row) instead of full ones and a remainder: 33 rows as 11+11+11, not 16+16+1
@@ -1413,10 +1479,19 @@ static int fwd_plan(DwParams& p, int per_cu = 8, bool window5 = false, int tw5 =
   return kind;
 }
 
-template <int KS, int PRO>
+// the weight gradient's plan, over dw_conv_problem
+static int dw_plan_wgrad(DwParams& p) {
+  static const int dww_per_cu = env_int("DL3P_DWW_PER_CU", 2);   // fewer slabs: the slab reduce costs as much as the kernel at 8
+  // 5x5 stride 1: rolling-row kernel (kind 1) with strips of DL3P_DW5_WROWS (1 | 2) columns -- p.tw says which --, 0 = per-pixel gather
+  static const int wrows = env_int("DL3P_DW5_WROWS", 2);
+  const bool rows5 = p.ks5 && p.stride == 1 && wrows > 0;
+  return dw_plan(p, DW_WGRAD, {dww_per_cu, rows5, wrows});
+}
+
+template <int PRO>
 static void launch_fwd_pro(const DwParams& p, int kind, dim3 grid, hipStream_t st) {
   dim3 block(256);
-  if (KS == 5) {
+  if (p.ks5) {
     // 5x5: narrower strips (window = 5 rows) and the weights in LDS (25 x c4s float4)
     const size_t lds = (size_t)25 * p.c4s * sizeof(float4);
     const int rows_tw = dw5_rows_tw(ceil_div(p.Wo, p.rate));
@@ -1458,29 +1533,12 @@ static void launch_fwd_pro(const DwParams& p, int kind, dim3 grid, hipStream_t s
   else dl3p_launch(dw_fwd_gather<3, PRO>, grid, block, 0, st, p);
 }
 
-// lanes + work decomposition of a forward-role launch (also what dl3p_dwconv2d_fwd reports as partial rows)
-static int plan_forward(DwParams& p, int KS, int tw5) {
-  p.ks = KS;
-  p.ks5 = KS == 5;
-  static const int dwf_per_cu = env_int("DL3P_DWF_PER_CU", 8);
-  if (KS == 5) {          // keep the LDS weight tile small: at most 64 channel lanes per workgroup
-    const int c4 = p.C / 4;
-    int best = 1;
-    for (int d = 1; d <= c4 && d <= 64; ++d)
-      if (c4 % d == 0 && (256 / d) * d >= (256 / best) * best) best = d;
-    p.c4s = best; p.px = 256 / best; p.nslab = c4 / best;
-  }
-  return fwd_plan(p, dwf_per_cu, true, tw5);
-}
-
-template <int KS>
-static void launch_fwd(const DwParams& p0, hipStream_t st) {
-  DwParams p = p0;
-  const int kind = plan_forward(p, KS, 0);
+// the launch of a planned forward or flipped problem (role DW_FWD or DW_DGRAD)
+static void launch_fwd(DwParams p, int kind, DwRole role, hipStream_t st) {
   // streaming stores for forward outputs (bit 0 window kernels, bit 1 gather): -0.09 ms per step, and the rate-18
   // lattice kernel (always streaming) keeps its input in L2: 9.6 -> 8.8 us in-step
   static const int nt_mask = env_int("DL3P_DW_NT", 3);
-  p.nt = (p.flip == 0 && !p.accumulate) ? ((kind == 0 ? (nt_mask >> 1) : nt_mask) & 1) : 0;
+  p.nt = (role == DW_FWD && !p.accumulate) ? ((kind == 0 ? (nt_mask >> 1) : nt_mask) & 1) : 0;
   // counted-wait rows (dw_fwd_seg FAST): measured on MI355X they pay where the row's stores are slow to retire -- the STREAMING stores
   // of forward launches on tensors far beyond the caches (decoder_conv0 / conv1_depthwise at batch 16: 142.9 -> 137.5, 127.4 -> 108.0 us)
   // -- and lose 10-15 % on cache-sized tensors and on every data gradient (plain stores retire at L2 anyway).  DL3P_DW_FAST_ROWS:
@@ -1490,75 +1548,62 @@ static void launch_fwd(const DwParams& p0, hipStream_t st) {
   p.fast_rows = fast_rows >= 2 || (fast_rows == 1 && p.nt && out_bytes >= (200ll << 20));
   dim3 grid(p.nbx * p.nslab);
   const int pro = (p.act != DL3P_ACT_NONE) ? 2 : (p.scale ? 1 : 0);
-  if (pro == 2) launch_fwd_pro<KS, 2>(p, kind, grid, st);
-  else if (pro == 1) launch_fwd_pro<KS, 1>(p, kind, grid, st);
-  else launch_fwd_pro<KS, 0>(p, kind, grid, st);
+  if (pro == 2) launch_fwd_pro<2>(p, kind, grid, st);
+  else if (pro == 1) launch_fwd_pro<1>(p, kind, grid, st);
+  else launch_fwd_pro<0>(p, kind, grid, st);
 }
 
 // ---- an input whose first channels are a bilinear upsampling formed on the fly (DwParams::up_x)
-static thread_local DwParams t_dw_up = {};
+// The description is armed by dl3p_dw_upsampled_input and applies to ONE call: the consuming entry points take it (dw_take_up) as
+// their first action, before any check that can return, so a refused call never leaves it armed for the next one.
+struct DwUp { const float* x; int ld, h, w, C; };
+static thread_local DwUp t_dw_up = {};
 extern "C" int dl3p_dw_upsampled_input(const float* up_x, int up_ld, int up_h, int up_w, int up_C, void* stream) {
   (void)stream;          // (every entry of a launch list ends in the stream)
   DL3P_CHECK_ARG(up_x && aligned16(up_x) && up_ld % 4 == 0 && up_C > 0 && up_C % 4 == 0 && up_ld >= up_C && up_h > 0 && up_w > 0,
                  "dl3p_dw_upsampled_input: bad arguments");
-  t_dw_up.up_x = up_x; t_dw_up.up_ld = up_ld; t_dw_up.up_h = up_h; t_dw_up.up_w = up_w; t_dw_up.up_C = up_C;
+  t_dw_up = {up_x, up_ld, up_h, up_w, up_C};
   return DL3P_OK;
 }
-static int plan_forward(DwParams& p, int KS, int tw5);
-static int dwconv2d_bwd_weight_impl(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act, const float* dy,
-                                    int lddy, float* gw, float* workspace, size_t workspace_bytes, int N, int H, int W, int C, int k,
-                                    int stride, int rate, int pad_t, int pad_l, int Ho, int Wo, int* rows_out, void* stream,
-                                    const DwParams* fold, int* kind_out);
+static DwUp dw_take_up() {
+  const DwUp up = t_dw_up;
+  t_dw_up.x = nullptr;
+  return up;
+}
+static void dw_set_up(DwParams& p, const DwUp& up) {
+  p.up_x = up.x; p.up_ld = up.ld; p.up_h = up.h; p.up_w = up.w; p.up_C = up.C;
+}
 // role 0: dl3p_dwconv2d_fwd, 1: dl3p_dwconv2d_bwd_weight_slabs[_bn] -- is the launch one of the 3x3 stride-1 window kernels that carry
 // the UP form (the caller's prologue must be a BatchNorm affine + activation)?
 extern "C" int dl3p_dw_upsampled_input_supported(int role, int N, int H, int W, int C, int up_C, int k, int stride, int rate, int pad_t,
                                                  int pad_l, int Ho, int Wo) {
   if (k != 3 || stride != 1 || rate != 1 || C <= 0 || C % 4 || up_C <= 0 || up_C % 4 || up_C > C || N <= 0 || H <= 0 || W <= 0) return 0;
-  DwParams p = {};
-  p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-  if (role == 0) {
-    pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-    return plan_forward(p, 3, 0) == 1;
-  }
-  int kind = -1;
-  alignas(16) static float dummy[4];
-  const int rc = dwconv2d_bwd_weight_impl(dummy, C, nullptr, nullptr, DL3P_ACT_NONE, dummy, C, dummy, dummy, (size_t)-1, N, H, W, C, k,
-                                          stride, rate, pad_t, pad_l, Ho, Wo, nullptr, nullptr, nullptr, &kind);
-  return rc == DL3P_OK && kind == 1;
-}
-// (consumes the armed description: it applies to ONE call)
-static bool dw_take_up(DwParams& p) {
-  if (!t_dw_up.up_x) return false;
-  p.up_x = t_dw_up.up_x; p.up_ld = t_dw_up.up_ld; p.up_h = t_dw_up.up_h; p.up_w = t_dw_up.up_w; p.up_C = t_dw_up.up_C;
-  t_dw_up.up_x = nullptr;
-  return true;
+  const DwGeom g = {N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo};
+  DwParams p = role == 0 ? dw_forward_problem(g) : dw_conv_problem(g);
+  return (role == 0 ? dw_plan(p, DW_FWD, dw_forward_opts()) : dw_plan_wgrad(p)) == 1;
 }
 
 extern "C" int dl3p_dwconv2d_fwd(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
                                  const float* w, float* y, int ldy, float* stat_partials, int* rows_out,
                                  int N, int H, int W, int C, int k, int stride, int rate, int pad_t, int pad_l,
                                  int Ho, int Wo, void* stream) {
+  const DwUp up = dw_take_up();
   int rc = check_dw_common("dl3p_dwconv2d_fwd", x, ldx, C, k);
   if (rc) return rc;
   DL3P_CHECK_ARG(x && w && y, "dl3p_dwconv2d_fwd: null pointer");
   DL3P_CHECK_ARG(ldy % 4 == 0 && ldy >= C && aligned16(y) && aligned16(w), "dl3p_dwconv2d_fwd: bad y/w layout");
   DL3P_CHECK_ARG(N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && stride >= 1 && rate >= 1, "dl3p_dwconv2d_fwd: bad dims");
-  DwParams p = {};
+  DwParams p = dw_forward_problem({N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo});
   p.x = x; p.ldx = ldx; p.scale = in_scale; p.shift = in_shift; p.act = in_act; p.w = w;
   p.y = y; p.ldy = ldy; p.partials = stat_partials;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate;
-  p.pad_t = pad_t; p.pad_l = pad_l;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  const bool up = dw_take_up(p);
-  {
-    DwParams q = p;
-    const int kind = plan_forward(q, k, 0);
-    if (rows_out) *rows_out = q.nbx;
-    DL3P_CHECK_ARG(!up || (k == 3 && stride == 1 && rate == 1 && kind == 1 && in_scale && in_act != DL3P_ACT_NONE && p.up_C <= C),
+  const int kind = dw_plan(p, DW_FWD, dw_forward_opts());
+  if (rows_out) *rows_out = p.nbx;
+  if (up.x) {
+    DL3P_CHECK_ARG(k == 3 && stride == 1 && rate == 1 && kind == 1 && in_scale && in_act != DL3P_ACT_NONE && up.C <= C,
                    "dl3p_dwconv2d_fwd: the upsampled-input form serves 3x3 stride-1 window launches behind a BatchNorm + activation (dl3p_dw_upsampled_input_supported)");
+    dw_set_up(p, up);
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (k == 3) launch_fwd<3>(p, st); else launch_fwd<5>(p, st);
+  launch_fwd(p, kind, DW_FWD, (hipStream_t)stream);
   DL3P_CHECK_LAUNCH("dl3p_dwconv2d_fwd");
   return DL3P_OK;
 }
@@ -1571,32 +1616,20 @@ extern "C" int dl3p_dwconv2d_bwd_data(const float* dy, int lddy, const float* w,
   DL3P_CHECK_ARG(dy && w && gx, "dl3p_dwconv2d_bwd_data: null pointer");
   DL3P_CHECK_ARG(ldgx % 4 == 0 && ldgx >= C && aligned16(gx) && aligned16(w), "dl3p_dwconv2d_bwd_data: bad gx/w layout");
   hipStream_t st = (hipStream_t)stream;
-  DwParams p = {};
-  p.w = w; p.C = C; p.N = N; p.accumulate = accumulate;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
+  const DwGeom g = {N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo};
   if (stride == 1) {
-    // correlation with the flipped kernel: a forward conv from (Ho,Wo) to (H,W) with
-    // pad' = rate*(k-1) - pad
-    p.x = dy; p.ldx = lddy; p.y = gx; p.ldy = ldgx; p.flip = 1;
-    p.H = Ho; p.W = Wo; p.Ho = H; p.Wo = W; p.stride = 1; p.rate = rate;
-    p.pad_t = rate * (k - 1) - pad_t; p.pad_l = rate * (k - 1) - pad_l;
-    p.act = DL3P_ACT_NONE;
-    if (k == 3) launch_fwd<3>(p, st); else launch_fwd<5>(p, st);
+    DwParams p = dw_flipped_problem(g);
+    p.x = dy; p.ldx = lddy; p.w = w; p.y = gx; p.ldy = ldgx; p.accumulate = accumulate;
+    const int kind = dw_plan(p, DW_DGRAD, dw_forward_opts());
+    launch_fwd(p, kind, DW_DGRAD, st);
   } else {
-    p.dy = dy; p.lddy = lddy; p.y = gx; p.ldy = ldgx;
-    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
+    DwParams p = dw_strided_dgrad_problem(g);
+    p.dy = dy; p.lddy = lddy; p.w = w; p.y = gx; p.ldy = ldgx; p.accumulate = accumulate;
+    dim3 grid(p.nbx * p.nslab), block(256);
     if (stride == 2 && rate == 1) {
-      p.th = ((H - 1 + pad_t) >> 1) + 1;     // quads per column
-      p.spr = ((W - 1 + pad_l) >> 1) + 1;    // quads per row
-      p.total = (long long)N * p.th * p.spr;
-      p.nbx = pick_nbx(p.total, p.px, p.nslab);
-      dim3 grid(p.nbx * p.nslab), block(256);
       if (k == 3) hipLaunchKernelGGL((dw_bwd_data_s2<3>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((dw_bwd_data_s2<5>), grid, block, 0, st, p);
     } else {
-      p.total = (long long)N * H * W;
-      p.nbx = pick_nbx(p.total, p.px, p.nslab);
-      dim3 grid(p.nbx * p.nslab), block(256);
       if (k == 3) hipLaunchKernelGGL((dw_bwd_data_strided<3>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((dw_bwd_data_strided<5>), grid, block, 0, st, p);
     }
@@ -1625,35 +1658,30 @@ extern "C" int dl3p_dwconv2d_bwd_data_bn(const float* dy, int lddy, const float*
   DL3P_CHECK_ARG(ldgx % 4 == 0 && ldgx >= C && ldz % 4 == 0 && ldz >= C && aligned16(gx) && aligned16(w) && aligned16(z),
                  "dl3p_dwconv2d_bwd_data_bn: bad gx/z/w layout");
   hipStream_t st = (hipStream_t)stream;
-  DwParams p = {};
-  p.w = w; p.C = C; p.N = N; p.accumulate = accumulate; p.partials = partials;
-  p.bb_z = z; p.bb_ldz = ldz; p.bb_scale = scale; p.bb_shift = shift; p.bb_mean = save_mean; p.bb_invstd = save_invstd;
-  p.bb_act = act;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  bool fused = false;
+  const DwGeom g = {N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo};
+  const auto with_sums = [&](DwParams p) {
+    p.w = w; p.y = gx; p.ldy = ldgx; p.accumulate = accumulate; p.partials = partials;
+    p.bb_z = z; p.bb_ldz = ldz; p.bb_scale = scale; p.bb_shift = shift; p.bb_mean = save_mean; p.bb_invstd = save_invstd;
+    p.bb_act = act;
+    return p;
+  };
+  int rows = 0;
   if (stride == 1 && k == 3) {
-    p.x = dy; p.ldx = lddy; p.y = gx; p.ldy = ldgx; p.flip = 1;
-    p.H = Ho; p.W = Wo; p.Ho = H; p.Wo = W; p.stride = 1; p.rate = rate;
-    p.pad_t = rate * (k - 1) - pad_t; p.pad_l = rate * (k - 1) - pad_l;
-    p.act = DL3P_ACT_NONE;
-    const int kind = plan_forward(p, k, 0);
-    if (kind == 1) {
+    DwParams p = with_sums(dw_flipped_problem(g));
+    p.x = dy; p.ldx = lddy;
+    if (dw_plan(p, DW_DGRAD_BN, dw_forward_opts()) == 1) {
       if (p.tw == 2) dl3p_launch(dw_fwd_seg<3, 2, 1, 0, true>, dim3(p.nbx * p.nslab), dim3(256), 0, st, p);
       else dl3p_launch(dw_fwd_seg<3, 4, 1, 0, true>, dim3(p.nbx * p.nslab), dim3(256), 0, st, p);
-      fused = true;
+      rows = p.nbx;
     }
   } else if (stride == 2 && rate == 1 && k == 3) {
-    p.dy = dy; p.lddy = lddy; p.y = gx; p.ldy = ldgx;
-    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-    p.th = ((H - 1 + pad_t) >> 1) + 1;
-    p.spr = ((W - 1 + pad_l) >> 1) + 1;
-    p.total = (long long)N * p.th * p.spr;
-    p.nbx = pick_nbx(p.total, p.px, p.nslab);
+    DwParams p = with_sums(dw_strided_dgrad_problem(g));
+    p.dy = dy; p.lddy = lddy;
     hipLaunchKernelGGL((dw_bwd_data_s2<3, true>), dim3(p.nbx * p.nslab), dim3(256), 0, st, p);
-    fused = true;
+    rows = p.nbx;
   }
-  if (fused) {
-    *rows_out = p.nbx;
+  if (rows) {          // fused
+    *rows_out = rows;
     DL3P_CHECK_LAUNCH("dl3p_dwconv2d_bwd_data_bn");
     return DL3P_OK;
   }
@@ -1678,11 +1706,13 @@ static void launch_bwdw_bna(const DwParams& p, int kind, dim3 grid, hipStream_t 
   else hipLaunchKernelGGL((dw_bwd_weight_seg<3, 2, 2, PRO, true>), grid, block, 0, st, p);
 }
 
-template <int KS, int PRO>
+template <int PRO>
 static void launch_bwdw(const DwParams& p, int kind, dim3 grid, hipStream_t st) {
   dim3 block(256);
-  if (KS == 5) {     // 25 tap accumulators + a 5-row window do not fit the register file: per-pixel gather only
-    hipLaunchKernelGGL((dw_bwd_weight<5, PRO>), grid, block, 0, st, p);
+  if (p.ks5) {     // 25 tap accumulators + a 5-row window do not fit the register file: rolling rows (dw_plan_wgrad) or the per-pixel gather
+    if (kind == 1 && p.tw == 1) hipLaunchKernelGGL((dw5_wgrad_rows<1, PRO>), grid, block, 0, st, p);
+    else if (kind == 1) hipLaunchKernelGGL((dw5_wgrad_rows<2, PRO>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((dw_bwd_weight<5, PRO>), grid, block, 0, st, p);
     return;
   }
   if (p.up_x) {
@@ -1695,7 +1725,7 @@ static void launch_bwdw(const DwParams& p, int kind, dim3 grid, hipStream_t st) 
   if (kind == 1 && p.tw == 2) hipLaunchKernelGGL((dw_bwd_weight_seg<3, 2, 1, PRO>), grid, block, 0, st, p);
   else if (kind == 1) hipLaunchKernelGGL((dw_bwd_weight_seg<3, 4, 1, PRO>), grid, block, 0, st, p);
   else if (kind == 2) hipLaunchKernelGGL((dw_bwd_weight_seg<3, 2, 2, PRO>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((dw_bwd_weight<3, PRO>), grid, block, 0, st, p);   // kind 0 (ks == 0 there: no kind 3)
+  else hipLaunchKernelGGL((dw_bwd_weight<3, PRO>), grid, block, 0, st, p);   // kind 0 (DW_WGRAD is never planned kind 3)
 }
 
 extern "C" size_t dl3p_dwconv2d_bwd_weight_workspace(int N, int Ho, int Wo, int C, int k) {
@@ -1704,12 +1734,13 @@ extern "C" size_t dl3p_dwconv2d_bwd_weight_workspace(int N, int Ho, int Wo, int 
   return (size_t)DL3P_MAX_STAT_ROWS * k * k * C * sizeof(float);   // one partial row per workgroup, at most
 }
 
-// rows_out != NULL: leave the partial rows in the workspace for dl3p_reduce_rows_batched (gw unused) and report how many
-static int dwconv2d_bwd_weight_impl(const float* x, int ldx, const float* in_scale, const float* in_shift,
+// rows_out != NULL: leave the partial rows in the workspace for dl3p_reduce_rows_batched (gw unused) and report how many.
+// up: what the entry point took with dw_take_up as its first action
+static int dwconv2d_bwd_weight_impl(const DwUp& up, const float* x, int ldx, const float* in_scale, const float* in_shift,
                                     int in_act, const float* dy, int lddy, float* gw, float* workspace,
                                     size_t workspace_bytes, int N, int H, int W, int C, int k, int stride,
                                     int rate, int pad_t, int pad_l, int Ho, int Wo, int* rows_out, void* stream,
-                                    const DwParams* fold, int* kind_out) {
+                                    const DwParams* fold) {
   int rc = check_dw_common("dl3p_dwconv2d_bwd_weight", x, ldx, C, k);
   if (rc) return rc;
   DL3P_CHECK_ARG(x && dy && (gw || rows_out) && workspace, "dl3p_dwconv2d_bwd_weight: null pointer");
@@ -1721,45 +1752,25 @@ static int dwconv2d_bwd_weight_impl(const float* x, int ldx, const float* in_sca
     return DL3P_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  DwParams p = {};
+  DwParams p = dw_conv_problem({N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo});
   p.x = x; p.ldx = ldx; p.scale = in_scale; p.shift = in_shift; p.act = in_act;
   p.dy = dy; p.lddy = lddy; p.partials = workspace;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate;
-  p.pad_t = pad_t; p.pad_l = pad_l;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  p.ks5 = k == 5;
-  static const int dww_per_cu = env_int("DL3P_DWW_PER_CU", 2);   // fewer slabs: the slab reduce costs as much as the kernel at 8
-  // 5x5 stride 1: rolling-row kernel with strips of DL3P_DW5_WROWS (1 | 2) columns, 0 = per-pixel gather
-  static const int wrows = env_int("DL3P_DW5_WROWS", 2);
-  const bool rows5 = k == 5 && stride == 1 && wrows > 0;
-  const int kind = fwd_plan(p, dww_per_cu, rows5, wrows);
-  if (kind_out) { *kind_out = kind; return DL3P_OK; }      // plan query (dl3p_dwconv2d_bwd_weight_bn_supported)
+  const int kind = dw_plan_wgrad(p);
   dim3 grid(p.nbx * p.nslab);
   const int pro = (in_act != DL3P_ACT_NONE) ? 2 : (in_scale ? 1 : 0);
-  if (dw_take_up(p))
-    DL3P_CHECK_ARG(k == 3 && stride == 1 && rate == 1 && kind == 1 && pro == 2 && p.up_C <= C,
+  if (up.x) {
+    DL3P_CHECK_ARG(k == 3 && stride == 1 && rate == 1 && kind == 1 && pro == 2 && up.C <= C,
                    "dl3p_dwconv2d_bwd_weight: the upsampled-input form serves 3x3 stride-1 window launches behind a BatchNorm + activation");
+    dw_set_up(p, up);
+  }
   if (fold) {
     DL3P_CHECK_ARG(k == 3 && (kind == 1 || kind == 2), "dl3p_dwconv2d_bwd_weight_slabs_bn: geometry not served by the window kernels");
     p.fa_z = fold->fa_z; p.fa_ldz = fold->fa_ldz; p.fa_scale = fold->fa_scale; p.fa_shift = fold->fa_shift;
     p.fa_mean = fold->fa_mean; p.fa_invstd = fold->fa_invstd; p.fa_coef = fold->fa_coef; p.fa_act = fold->fa_act;
     p.fa_dz = fold->fa_dz; p.fa_lddz = fold->fa_lddz;
     if (pro == 2) launch_bwdw_bna<2>(p, kind, grid, st); else if (pro == 1) launch_bwdw_bna<1>(p, kind, grid, st); else launch_bwdw_bna<0>(p, kind, grid, st);
-  } else if (rows5 && kind == 1) {
-    dim3 block(256);
-    if (wrows == 1) {
-      if (pro == 2) hipLaunchKernelGGL((dw5_wgrad_rows<1, 2>), grid, block, 0, st, p);
-      else if (pro == 1) hipLaunchKernelGGL((dw5_wgrad_rows<1, 1>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((dw5_wgrad_rows<1, 0>), grid, block, 0, st, p);
-    } else {
-      if (pro == 2) hipLaunchKernelGGL((dw5_wgrad_rows<2, 2>), grid, block, 0, st, p);
-      else if (pro == 1) hipLaunchKernelGGL((dw5_wgrad_rows<2, 1>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((dw5_wgrad_rows<2, 0>), grid, block, 0, st, p);
-    }
-  } else if (k == 3) {
-    if (pro == 2) launch_bwdw<3, 2>(p, kind, grid, st); else if (pro == 1) launch_bwdw<3, 1>(p, kind, grid, st); else launch_bwdw<3, 0>(p, kind, grid, st);
   } else {
-    if (pro == 2) launch_bwdw<5, 2>(p, kind, grid, st); else if (pro == 1) launch_bwdw<5, 1>(p, kind, grid, st); else launch_bwdw<5, 0>(p, kind, grid, st);
+    if (pro == 2) launch_bwdw<2>(p, kind, grid, st); else if (pro == 1) launch_bwdw<1>(p, kind, grid, st); else launch_bwdw<0>(p, kind, grid, st);
   }
   DL3P_CHECK_LAUNCH("dl3p_dwconv2d_bwd_weight");
   if (rows_out) { *rows_out = p.nbx; return DL3P_OK; }
@@ -1770,8 +1781,8 @@ extern "C" int dl3p_dwconv2d_bwd_weight(const float* x, int ldx, const float* in
                                         int in_act, const float* dy, int lddy, float* gw, float* workspace,
                                         size_t workspace_bytes, int N, int H, int W, int C, int k, int stride,
                                         int rate, int pad_t, int pad_l, int Ho, int Wo, void* stream) {
-  return dwconv2d_bwd_weight_impl(x, ldx, in_scale, in_shift, in_act, dy, lddy, gw, workspace, workspace_bytes, N, H, W, C, k,
-                                  stride, rate, pad_t, pad_l, Ho, Wo, nullptr, stream, nullptr, nullptr);
+  return dwconv2d_bwd_weight_impl(dw_take_up(), x, ldx, in_scale, in_shift, in_act, dy, lddy, gw, workspace, workspace_bytes, N, H, W,
+                                  C, k, stride, rate, pad_t, pad_l, Ho, Wo, nullptr, stream, nullptr);
 }
 
 // dl3p_dwconv2d_bwd_weight_slabs with the BatchNorm-backward apply of the conv's own output folded in (the depthwise
@@ -1780,11 +1791,9 @@ extern "C" int dl3p_dwconv2d_bwd_weight(const float* x, int ldx, const float* in
 extern "C" int dl3p_dwconv2d_bwd_weight_bn_supported(int N, int H, int W, int C, int k, int stride, int rate, int pad_t,
                                                      int pad_l, int Ho, int Wo) {
   if (k != 3 || C <= 0 || C % 4 || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return 0;
-  int kind = -1;
-  alignas(16) static float dummy[4];
-  const int rc = dwconv2d_bwd_weight_impl(dummy, C, nullptr, nullptr, DL3P_ACT_NONE, dummy, C, dummy, dummy, (size_t)-1, N, H, W, C,
-                                          k, stride, rate, pad_t, pad_l, Ho, Wo, nullptr, nullptr, nullptr, &kind);
-  return rc == DL3P_OK && (kind == 1 || kind == 2);
+  DwParams p = dw_conv_problem({N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo});
+  const int kind = dw_plan_wgrad(p);
+  return kind == 1 || kind == 2;
 }
 
 extern "C" int dl3p_dwconv2d_bwd_weight_slabs_bn(const float* x, int ldx, const float* in_scale, const float* in_shift,
@@ -1794,23 +1803,25 @@ extern "C" int dl3p_dwconv2d_bwd_weight_slabs_bn(const float* x, int ldx, const 
                                                  float* dz, int lddz, float* workspace, size_t workspace_bytes,
                                                  int* rows_out, int N, int H, int W, int C, int k, int stride, int rate,
                                                  int pad_t, int pad_l, int Ho, int Wo, void* stream) {
+  const DwUp up = dw_take_up();
   const char* fn = "dl3p_dwconv2d_bwd_weight_slabs_bn";
   DL3P_CHECK_ARG(rows_out && z && save_mean && save_invstd && coef && ldz % 4 == 0 && ldz >= C && aligned16(z) && dz != g &&
                      (!dz || (lddz % 4 == 0 && lddz >= C && aligned16(dz))), "%s: bad arguments", fn);
   DwParams f = {};
   f.fa_z = z; f.fa_ldz = ldz; f.fa_scale = bn_scale; f.fa_shift = bn_shift; f.fa_mean = save_mean; f.fa_invstd = save_invstd;
   f.fa_coef = coef; f.fa_act = bn_act; f.fa_dz = dz; f.fa_lddz = lddz;
-  return dwconv2d_bwd_weight_impl(x, ldx, in_scale, in_shift, in_act, g, ldg, nullptr, workspace, workspace_bytes, N, H, W, C, k,
-                                  stride, rate, pad_t, pad_l, Ho, Wo, rows_out, stream, &f, nullptr);
+  return dwconv2d_bwd_weight_impl(up, x, ldx, in_scale, in_shift, in_act, g, ldg, nullptr, workspace, workspace_bytes, N, H, W, C, k,
+                                  stride, rate, pad_t, pad_l, Ho, Wo, rows_out, stream, &f);
 }
 
 extern "C" int dl3p_dwconv2d_bwd_weight_slabs(const float* x, int ldx, const float* in_scale, const float* in_shift,
                                               int in_act, const float* dy, int lddy, float* workspace,
                                               size_t workspace_bytes, int* rows_out, int N, int H, int W, int C, int k,
                                               int stride, int rate, int pad_t, int pad_l, int Ho, int Wo, void* stream) {
+  const DwUp up = dw_take_up();
   DL3P_CHECK_ARG(rows_out != nullptr, "dl3p_dwconv2d_bwd_weight_slabs: rows_out is required");
-  return dwconv2d_bwd_weight_impl(x, ldx, in_scale, in_shift, in_act, dy, lddy, nullptr, workspace, workspace_bytes, N, H, W, C,
-                                  k, stride, rate, pad_t, pad_l, Ho, Wo, rows_out, stream, nullptr, nullptr);
+  return dwconv2d_bwd_weight_impl(up, x, ldx, in_scale, in_shift, in_act, dy, lddy, nullptr, workspace, workspace_bytes, N, H, W, C,
+                                  k, stride, rate, pad_t, pad_l, Ho, Wo, rows_out, stream, nullptr);
 }
 
 #include "dw_bf16_window.h"
@@ -1833,20 +1844,13 @@ int dl3p_dw_window_bf16(int role, const void* x, int ldx, const float* in_scale,
   // 5x5: the 2-column window kernel needs all 256 registers (one wave per SIMD) and loses to the strip kernels (64x128x960 rate 2:
   // 44.7 against 38.6 us); stride 2 ties.  3x3 only.
   if (k != 3) return 0;
-  DwParams p = {};
+  const DwGeom g = {N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo};
+  DwParams p = role == 0 ? dw_forward_problem(g) : dw_flipped_problem(g);
   p.bf16_io = 1;
   p.x = reinterpret_cast<const float*>(x); p.ldx = ldx; p.w = reinterpret_cast<const float*>(w);
-  p.y = reinterpret_cast<float*>(y); p.ldy = ldy; p.C = C; p.N = N; p.accumulate = accumulate;
-  if (role == 0) {
-    p.scale = in_scale; p.shift = in_shift; p.act = in_act; p.partials = partials;
-    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-  } else {
-    p.flip = 1; p.act = DL3P_ACT_NONE;
-    p.H = Ho; p.W = Wo; p.Ho = H; p.Wo = W; p.stride = 1; p.rate = rate;
-    p.pad_t = rate * (k - 1) - pad_t; p.pad_l = rate * (k - 1) - pad_l;
-  }
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  const int kind = plan_forward(p, k, 2);
+  p.y = reinterpret_cast<float*>(y); p.ldy = ldy; p.accumulate = accumulate;
+  if (role == 0) { p.scale = in_scale; p.shift = in_shift; p.act = in_act; p.partials = partials; }
+  const int kind = dw_plan(p, role == 0 ? DW_FWD : DW_DGRAD, dw_forward_opts(2));   // (5x5 strip width: dwb_fwd_seg<5, 2, 1>)
   if (kind != 1 && kind != 2) return 0;
   if (rows_out) *rows_out = p.nbx;
   const dim3 grid(p.nbx * p.nslab), block(256);
@@ -1877,14 +1881,11 @@ int dl3p_dw_window_wgrad_bf16(const void* x, int ldx, const float* in_scale, con
   // few pixels (Xception's 33 x 33 maps at batch 4: 4356): the strip kernel's finer work items fill the chip better -- 27.4 against
   // 34.2 us on 33 x 33 x 728; from 65 x 65 x 4 up the window kernel ties or wins (129 x 129 x 256 stride 2: 35.5 against 49.5)
   if ((long long)N * Ho * Wo < 16384) return 0;
-  DwParams p = {};
+  DwParams p = dw_conv_problem({N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo});
   p.bf16_io = 1;
   p.x = reinterpret_cast<const float*>(x); p.ldx = ldx; p.scale = in_scale; p.shift = in_shift; p.act = in_act;
   p.dy = reinterpret_cast<const float*>(dy); p.lddy = lddy; p.partials = workspace;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  p.ks = 3;
-  const int kind = fwd_plan(p, 2, false, 0);
+  const int kind = dw_plan(p, DW_WGRAD, {2, false, 0});      // (per_cu fixed at 2 here: DL3P_DWW_PER_CU is the fp32 entry's)
   if (kind != 1 && kind != 2) return 0;
   if (p.nbx > max_rows) p.nbx = max_rows / DL3P_NUM_XCDS * DL3P_NUM_XCDS;      // the workspace's rows (a multiple of the XCD count stays one)
   const dim3 grid(p.nbx * p.nslab), block(256);
@@ -1909,34 +1910,15 @@ extern "C" int dl3p_dw_plan_query(int role, int N, int H, int W, int C, int k, i
   DL3P_CHECK_ARG(out6 && role >= 0 && role <= 3 && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (k == 3 || k == 5) &&
                      stride >= 1 && rate >= 1 && Ho > 0 && Wo > 0, "dl3p_dw_plan_query: bad arguments");
   for (int i = 0; i < 6; ++i) out6[i] = 0;
-  alignas(16) static float dummy[4];
-  DwParams p = {};
-  p.C = C; p.N = N; p.w = dummy;
-  pick_lanes(C, &p.c4s, &p.px, &p.nslab);
-  int kind;
-  if (role == 0) {
-    p.x = dummy; p.ldx = C; p.y = dummy; p.ldy = C;
-    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-    kind = plan_forward(p, k, 0);
-  } else if (role == 1 || role == 2) {
-    if (role == 2) p.bb_z = dummy;
-    if (stride == 1 && (role == 1 || k == 3)) {
-      p.x = dummy; p.ldx = C; p.y = dummy; p.ldy = C; p.flip = 1;
-      p.H = Ho; p.W = Wo; p.Ho = H; p.Wo = W; p.stride = 1; p.rate = rate;
-      p.pad_t = rate * (k - 1) - pad_t; p.pad_l = rate * (k - 1) - pad_l;
-      kind = plan_forward(p, k, 0);
-    } else {
-      out6[0] = 4;          // stride-2 quads / strided gather of the data gradient: no row bands, no table
-      return DL3P_OK;
-    }
-  } else {
-    p.x = dummy; p.ldx = C; p.dy = dummy; p.lddy = C;
-    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.rate = rate; p.pad_t = pad_t; p.pad_l = pad_l;
-    p.ks5 = k == 5;
-    static const int dww_per_cu = env_int("DL3P_DWW_PER_CU", 2);
-    static const int wrows = env_int("DL3P_DW5_WROWS", 2);
-    kind = fwd_plan(p, dww_per_cu, k == 5 && stride == 1 && wrows > 0, wrows);
+  const DwGeom g = {N, H, W, C, k, stride, rate, pad_t, pad_l, Ho, Wo};
+  const DwRole r = (DwRole)role;
+  if ((r == DW_DGRAD || r == DW_DGRAD_BN) && !(stride == 1 && (r == DW_DGRAD || k == 3))) {
+    out6[0] = 4;          // stride-2 quads / strided gather of the data gradient, 5x5 without fused sums: no row bands, no table
+    return DL3P_OK;
   }
-  out6[0] = kind; out6[1] = p.tw; out6[2] = p.th; out6[3] = p.nbands; out6[4] = p.nbx; out6[5] = dw_tuned_lookup(p) != nullptr;
+  DwParams p = r == DW_WGRAD ? dw_conv_problem(g) : (r == DW_FWD ? dw_forward_problem(g) : dw_flipped_problem(g));
+  p.ldx = p.ldy = C;          // dense tensors
+  const int kind = r == DW_WGRAD ? dw_plan_wgrad(p) : dw_plan(p, r, dw_forward_opts());
+  out6[0] = kind; out6[1] = p.tw; out6[2] = p.th; out6[3] = p.nbands; out6[4] = p.nbx; out6[5] = dw_tuned_lookup(p, r) != nullptr;
   return DL3P_OK;
 }
