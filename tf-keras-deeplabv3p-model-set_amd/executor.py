@@ -14,19 +14,16 @@ PyTorch only provides memory, streams, graphs and torch.distributed here.
 import collections
 import contextlib
 import ctypes
-import os
 import zlib
 import numpy as np
 import torch
 
 from ._lib import lib
+from .exec_options import GHOST_ON_BY_DEFAULT, ExecOptions       # noqa: F401  (every DL3P_* switch of this file: exec_options.ROWS)
 from .graph import ACT_NONE, ACT_RELU
 
 MAX_ROWS = 2048
-# The fused ghost-module forward (Executor._find_ghost) has NOT been measured against the pair of launches it replaces
-# (scripts/bench_ghost.py is the measurement; docs/experiments.md), so it is opt-in: DL3P_GHOST=1 fuses the module shapes the
-# kernel was built for, from GHOST_MIN_ROWS pixels per batch (N*H*W) up.  A measured table turns this into the default rule.
-GHOST_ON_BY_DEFAULT = False
+# the module shapes (K, c) the fused ghost forward was built for, and from how many pixels per batch (N*H*W): the `ghost` rows
 GHOST_DEFAULT = {(16, 8), (16, 24), (48, 12), (24, 36), (72, 12)}
 GHOST_MIN_ROWS = 0
 
@@ -44,12 +41,8 @@ FoldedDg = collections.namedtuple('FoldedDg', Folded._fields + ('dz', 'lddz'))
 
 
 def split_gemm_enabled():
-    """The compute-bound pointwise convs (K >= 128, N >= 128, >= 16384 rows) run as fp32-accurate split-bf16 GEMMs on the bf16
-    matrix pipe (csrc/pw_split.hip): every fp32 operand split exactly into three bf16 pieces, six cross products
-    accumulated in fp32 -- parity held at the tolerances of the fp32-input MFMA kernels (tests/test_split_gemm_gpu.py, and the whole
-    GPU suite runs with it).  On by default since round 3; DL3P_SPLIT_GEMM=0 (bench.py --split-gemm 0), read when the parameter
-    store is built, keeps every GEMM on the fp32-input MFMA kernels."""
-    return os.environ.get('DL3P_SPLIT_GEMM', '1') not in ('', '0')
+    """the `split_gemm` row of exec_options.py, for the parameter store: it is built before any executor"""
+    return ExecOptions.from_env().split_gemm
 
 
 class ParamStore:
@@ -454,7 +447,6 @@ class BackwardTrace:
         self.fuse_add = {}            # ... through a residual Add (_bn_fusion_through_adds)
         self.presums = {}             # 'bn' op -> partial rows left in partials2 by such a data gradient
         self.galias = {}              # z tensor id -> (ptr, ld) of the buffer that already holds d/d(BN(z) output)
-        self.alias_ok = True
         self.defer = False            # SyncBatchNorm: weight gradients wait in `deferred` for the next all-reduce to hide behind
         self.deferred = []
         self.pending = []             # SyncBatchNorm: ('bn' op, staging offset, label) waiting for their all-reduce
@@ -477,6 +469,7 @@ class Executor:
                  seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
                  averaging=None, clip=None):
         self.g, self.head, self.store = graph, head, store
+        self.opts = ExecOptions.from_env()      # every switch, fixed now for the life of this executor (exec_options.py)
         # gradient clipping: None | (clipvalue, clipnorm, global_clipnorm) (model clip_spec()), traced in front of the optimiser
         self.clip = clip if training else None
         self._norm_host, self._norm_evt, self._norm_posted = None, None, None
@@ -490,9 +483,7 @@ class Executor:
         self.loss_kind = {'ce': 0, 'weighted': 1, 'focal': 2}[loss[0]]
         self.loss_gamma, self.loss_alpha = (float(loss[1]), float(loss[2])) if loss[0] == 'focal' else (0.0, 0.0)
         self._loss_weights_host = np.asarray(loss[1], np.float32) if loss[0] == 'weighted' else None
-        # DL3P_FORCE_DIST=1 exercises the collective path on a single rank (plumbing test)
-        force = bool(os.environ.get('DL3P_FORCE_DIST'))
-        self.dist = dist if (dist is not None and (dist.world_size > 1 or force)) else None
+        self.dist = dist if (dist is not None and (dist.world_size > 1 or self.opts.force_dist)) else None
         self.sync_bn = self.dist is not None and self.dist.sync_bn
         # optimizer: ('sgd', momentum) | ('adam', beta_1, beta_2, epsilon) | ('rmsprop', rho, epsilon)
         self.optimizer = optimizer or ('sgd', momentum)
@@ -522,12 +513,23 @@ class Executor:
         self._routes = {}                                    # conv op -> its kernel family (_route)
         # the weight gradients pick the split kernel inside the library (dl3p_pwconv_bwd_weight[_slabs], wgrad_sb_route): the switch
         # is process-wide there, so every executor states its own before it sizes workspaces, traces, or runs eagerly
-        self._split_wgrad = int(split_gemm_enabled() and not self.bf16 and os.environ.get('DL3P_SPLIT_WGRAD', '1') not in ('', '0'))
+        self._split_wgrad = int(self.opts.split_gemm and not self.bf16 and self.opts.split_wgrad)
         self.L.set_option(b'split_wgrad', self._split_wgrad)
         # ... and the other process-wide knobs that decide how many slabs / partial rows a traced launch writes: recorded now, pinned
         # again before every eager replay (_pin_options; a captured graph carries its launches' grids with it)
         self._pinned = {k: self.L.get_option(k) for k in (b'conv_sb', b'sb_rs', b'sb_pipe', b'splitk', b'sb3')}
         self._pinned_irb = tuple(self.L.irb_get_plan(i) for i in range(4))
+        # who reads what, for the three fusion passes: root tensor id -> [(op, slot, value)] in graph order, the 'bn' ops that take a
+        # root as their z (not a value slot: kept apart), and the tensors an activation view stands on
+        self._readers, self._z_readers = {}, {}
+        for op in graph.ops:
+            for slot in ('x', 'r', 's'):
+                v = getattr(op, slot, None)
+                if v is not None:
+                    self._readers.setdefault(v.tensor.root.id, []).append((op, slot, v))
+            if op.kind == 'bn':
+                self._z_readers.setdefault(op.z.root.id, []).append(op)
+        self._views = {t.id for (t, _, _) in graph.act_views.values()}
         self._find_irb()
         self._find_up()
         self._find_ghost()
@@ -574,7 +576,7 @@ class Executor:
             if t.id in direct_cols and not (t.id in grad_cols and self.training and t.requires_grad):
                 continue
             if t.id in self._irb_tensors:          # the expanded tensor of a fused inverted-residual block is never in HBM
-                if self._irb_keep_z:               # (test hook: a copy for the parity tests to look at; no kernel of the step reads it)
+                if self.opts.irb_debug_z:               # (test hook: a copy for the parity tests to look at; no kernel of the step reads it)
                     self.buf[t.id] = torch.zeros(N * t.H * t.W * t.C, dtype=dt, device=self.dev)
                 continue
             if not getattr(t, 'grad_only', False) and t.id not in direct_cols:
@@ -649,9 +651,6 @@ class Executor:
         self.labels = torch.zeros(N * H * W, **self.f32)
         self.loss_partials = torch.zeros(MAX_ROWS, **self.f32)
         self.loss = torch.zeros(1, **self.f32)
-        # The fused training heads (plain cross-entropy only).  dl3p_head_train_rows (x / y separable: a quarter of the full-resolution
-        # gradient's traffic) is the default where it is served; DL3P_FUSED_HEAD=0: the two-kernel path, =tile: dl3p_head_train (one
-        # launch, no workspace, bit-identical to the two-kernel path but measured slower: 506 us vs 141 + 165 us at batch 16).
         zt = self.head.tensor
         self.class_weights = None
         if self._loss_weights_host is not None:
@@ -662,7 +661,7 @@ class Executor:
         # per-image class counts for the Jaccard training metric (deeplabv3p/metrics.py:29-46), refreshed every step
         self.metric_counts = (torch.zeros(N * 3 * self.C, dtype=torch.int32, device=self.dev).view(N, 3, self.C)
                               if (self.training and self.want_class_counts) else None)
-        want = os.environ.get('DL3P_FUSED_HEAD', 'rows')
+        want = self.opts.fused_head       # the fused training heads, plain cross-entropy only: the `fused_head` row of exec_options.py
         plain = bool(self.training and self.loss_kind == 0 and not self.sample_weighted and
                      self.class_weights is None and zt is not None and zt.requires_grad)
         # (the logits and their gradient stay fp32 under the bf16 policy -- _is_f32 -- so the separable head serves it too; the padded
@@ -672,7 +671,7 @@ class Executor:
         self.nearest_head = getattr(g, 'head_upsample', 'bilinear') == 'nearest'
         plain = plain and not self.nearest_head
         self.fused_head_rows = bool(plain and want == 'rows' and L.head_train_rows_supported(zt.H, zt.W, self.C, H, W))
-        self.fused_head = self.fused_head_rows or bool(plain and not self.bf16 and want not in ('0', 'rows') and
+        self.fused_head = self.fused_head_rows or bool(plain and not self.bf16 and want == 'tile' and
                                                        L.head_train_supported(zt.H, zt.W, self.C, H, W))
         self.fused_head = self.fused_head or bool(self.nearest_head and self.training and zt.requires_grad)
         # depthwise-conv biases carried through their BatchNorm ('bn_bias' ops): per-channel constants of the two small launches
@@ -700,34 +699,18 @@ class Executor:
         block trainable (training) -- anything else keeps the unfused kernels.  Under SyncBatchNorm the expand BatchNorm's
         covariance sums (K + K*K doubles) and its backward sums travel in the same all-reduces as every other BatchNorm's"""
         self._irb_expand, self._irb_dw, self._irb_bn, self._irb_tensors = {}, {}, {}, set()
-        # DL3P_IRB_DEBUG_Z=1: the forward ALSO writes the expand output with the unfused kernel, for tests that inspect every conv
-        # output (activation branch patterns); the fused kernels never read it
-        self._irb_keep_z = os.environ.get('DL3P_IRB_DEBUG_Z', '0') == '1'
-        if self.bf16 or os.environ.get('DL3P_IRB', '1') == '0':
-            return
-        # the fused backward leaves its weight gradients as slabs for the batched slab reduction: with that switched off
-        # (DL3P_BATCHED_WGRAD=0, an A/B switch) a training executor keeps the unfused kernels
-        if self.training and os.environ.get('DL3P_BATCHED_WGRAD', '1') == '0':
+        opts = self.opts
+        # (the fused backward leaves its weight gradients as slabs for the batched slab reduction: without it, the unfused kernels)
+        if self.bf16 or not opts.irb or (self.training and not opts.batched_wgrad):
             return
         g, N, L = self.g, self.N, self.L
-        # measured on the headline step (DESIGN 4e): the 257 x 257 and 129 x 129 blocks pay (12.75 -> 12.22 ms), the 65 x 65 ones do not (12.47 with them)
-        min_rows = int(os.environ.get('DL3P_IRB_MIN_ROWS', '131072'))
-        readers = {}
-        for op in g.ops:
-            for slot in ('x', 'r', 's'):
-                v = getattr(op, slot, None)
-                if v is not None:
-                    readers.setdefault(v.tensor.root.id, []).append((op, slot, v))
-            if op.kind == 'bn':
-                readers.setdefault(op.z.root.id, []).append((op, 'z', None))
-        views = {t.id for (t, _, _) in g.act_views.values()}
+        min_rows = 131072 if opts.irb_min_rows is None else opts.irb_min_rows      # (measured: the `irb_min_rows` row)
         for e in g.ops:
             if e.kind != 'conv_pw' or e.b is not None or e.bn is None or e.out.base is not None or e.out is self.head.tensor:
                 continue
-            rd = readers.get(e.out.id, [])
-            if len(rd) != 2 or e.out.id in views:
+            rd, bn_ops = self._readers.get(e.out.id, []), self._z_readers.get(e.out.id, [])
+            if len(rd) + len(bn_ops) != 2 or e.out.id in self._views:
                 continue
-            bn_ops = [o for o, slot, _ in rd if o.kind == 'bn' and slot == 'z']
             dws = [(o, v) for o, slot, v in rd if o.kind == 'conv_dw' and slot == 'x']
             if len(bn_ops) != 1 or len(dws) != 1:
                 continue
@@ -737,9 +720,8 @@ class Executor:
             xt = e.x.tensor
             if N * xt.H * xt.W < min_rows or e.x.tensor.ld % 4 or xt.H != e.Ho or xt.W != e.Wo:
                 continue
-            # a stride-1 depthwise conv reaches every expanded pixel with all nine taps (a stride-2 one with 2.25 on average): the
-            # recomputing backward then costs what the unfused kernels cost (129 x 129 x 24 -> 144: 437 against 421 us per step)
-            if d.stride == 1 and N * xt.H * xt.W < int(os.environ.get('DL3P_IRB_S1_MIN_ROWS', '400000')) and 'DL3P_IRB_MIN_ROWS' not in os.environ:
+            # (a stride-1 block recomputes as much as the unfused kernels do: the `irb_s1_min_rows` row)
+            if d.stride == 1 and N * xt.H * xt.W < opts.irb_s1_min_rows and opts.irb_min_rows is None:
                 continue
             geo = (N, xt.H, xt.W, e.cin, e.cout, d.k, d.stride, d.rate, d.pad_t, d.pad_l, d.Ho, d.Wo)
             if d.c != e.cout or not L.irb_supported(*geo):
@@ -758,24 +740,17 @@ class Executor:
         (an inference executor, or both layers frozen in a training one) the pair is ONE dl3p_ghost_fwd launch (csrc/ghost_fwd.hip):
         z1 is stored and, in registers, fed to the depthwise conv instead of being read back.  The launch leaves exactly the
         tensors the pair leaves, so backward, taps and the weight gradients of non-frozen neighbours do not change.
-        self._ghost_pw / _ghost_dw: the two conv ops of a fused module -> (primary, bn op, cheap).  DL3P_GHOST=1 | 0 switches it
-        (GHOST_ON_BY_DEFAULT where unset); DL3P_GHOST_MIN_ROWS overrides the row threshold AND the shape table GHOST_DEFAULT
-        (DESIGN 4k)."""
+        self._ghost_pw / _ghost_dw: the two conv ops of a fused module -> (primary, bn op, cheap).  Switches: the `ghost` and
+        `ghost_min_rows` rows of exec_options.py."""
         self._ghost_pw, self._ghost_dw = {}, {}
-        if self.bf16 or os.environ.get('DL3P_GHOST', '1' if GHOST_ON_BY_DEFAULT else '0') == '0':
+        if self.bf16 or not self.opts.ghost:
             return
         g, N, L = self.g, self.N, self.L
-        pinned = 'DL3P_GHOST_MIN_ROWS' in os.environ
-        min_rows = int(os.environ['DL3P_GHOST_MIN_ROWS']) if pinned else GHOST_MIN_ROWS
+        pinned = self.opts.ghost_min_rows is not None
+        min_rows = self.opts.ghost_min_rows if pinned else GHOST_MIN_ROWS
         index = {id(op): i for i, op in enumerate(g.ops)}
-        readers = {}
-        for op in g.ops:
-            for slot in ('x', 'r', 's'):
-                v = getattr(op, slot, None)
-                if v is not None:
-                    readers.setdefault(v.tensor.root.id, []).append((op, slot, v))
+        readers, views = self._readers, self._views
         bn_ops = {id(op.bn): op for op in g.ops if op.kind == 'bn'}
-        views = {t.id for (t, _, _) in g.act_views.values()}
         for e in g.ops:
             if e.kind != 'conv_pw' or e.b is not None or e.bn is None or e.out.base is None or e.out.c0 != 0:
                 continue
@@ -823,19 +798,15 @@ class Executor:
         low-resolution map while they load (dl3p_dw_upsampled_input: the resize kernel's arithmetic, bit for bit) -- 272 MB less
         written and 2 x 272 MB less read per step at BASELINE configs[1].  self._up_conv: conv_dw op -> the resize op it absorbs"""
         self._up_conv, self._up_resize = {}, set()
-        # OPT-IN (DL3P_FOLD_RESIZE=1): built, bit-identical, and measured SLOWER on MI355X -- 12.62 against 12.02 ms per headline step
-        # (profiles/r06_resize_fold.txt): the fused forward takes 468 us against 140 + 80 for the pair it replaces.  Four dependent
-        # 16-byte loads and three lerps per input vector turn an HBM-bound window kernel (2 waves per SIMD at 217-256 registers) into
-        # a latency-bound one: the compiler serialises the conditional gathers (57 s_waitcnt vmcnt(0) in the loop against 9)
-        if self.bf16 or os.environ.get('DL3P_FOLD_RESIZE', '0') != '1':
+        # OPT-IN: built, bit-identical, and measured SLOWER on MI355X (the `fold_resize` row of exec_options.py has the numbers)
+        if self.bf16 or not self.opts.fold_resize:
             return
         g, N, L = self.g, self.N, self.L
         for r in g.ops:
             if r.kind != 'resize' or r.out.base is None or r.out.c0 != 0:
                 continue
             root = r.out.base
-            readers = [o for o in g.ops for slot in ('x', 'r', 's') if getattr(o, slot, None) is not None
-                       and getattr(o, slot).tensor.root is root and o is not r]
+            readers = [o for o, _, _ in self._readers.get(root.id, []) if o is not r]
             # (the other slices of the buffer are WRITTEN by their producers -- `out`, not a read -- and read through the root)
             if len(readers) != 1 or readers[0].kind != 'conv_dw':
                 continue
@@ -881,7 +852,7 @@ class Executor:
         return (not self.bf16 and op.b is None and v.is_plain
                 and not (xt.requires_grad or xt.root.requires_grad)
                 and self.L.stem_conv_supported(op.cin, op.cout, op.k, op.stride, op.rate)
-                and os.environ.get('DL3P_STEM_DIRECT', '1') != '0')
+                and self.opts.stem_direct)
 
     def _route(self, op):
         """the kernel family a conv runs on, decided once per op in the order the forward tests it: the two halves of a fused ghost
@@ -956,14 +927,13 @@ class Executor:
 
     def _narrow(self, op):
         """3x3 stride-1 'same' conv with Cout <= 32 and Cin <= 64 on the fp32 path (PeleeNet's dense layers): the direct
-        kernels of csrc/conv_narrow.hip, with DL3P_NARROW_CONV=1 only.  Off by default: measured slower than the implicit GEMM in
-        every role and at every PeleeNet shape (27.0 against 16.4 ms per 512 x 512 batch-16 step)."""
+        kernels of csrc/conv_narrow.hip.  Opt-in: the `narrow_conv` row of exec_options.py."""
         xt = op.x.tensor
         return bool(op.kind == 'conv_dense' and not self.bf16 and op.b is None and op.Ho == xt.H and op.Wo == xt.W
                     and op.pad_t == (op.k - 1) // 2 and op.pad_l == (op.k - 1) // 2 and op.cout == op.w.shape[3]
                     and not self._stem_direct(op)
                     and self.L.conv_narrow_supported(op.cin, op.cout, op.k, op.stride, op.rate)
-                    and os.environ.get('DL3P_NARROW_CONV', '0') == '1')
+                    and self.opts.narrow_conv)
 
     def _dense_gemm(self, op):
         """dense conv with Cin % 4 == 0 on the fp32 path: implicit GEMM, the patch operand gathered while the GEMM stages
@@ -1276,7 +1246,7 @@ class Executor:
                     self._irb_stage[op.bn] = off
                     sums = self.sync_stage[off:]
                 P.k(L.irb_cov_reduce, self.irb_cov_rows.data_ptr(), crow.value, op.cin, sums.data_ptr())
-            if self._irb_keep_z:
+            if self.opts.irb_debug_z:
                 P.k(L.pwconv_fwd_wt, *x, st.ptr(op.w, st.Pt), None, self.tptr(op.out), op.out.ld, None,
                     ctypes.byref(ctypes.c_int(0)), *self._mkn(op))
         else:
@@ -1518,14 +1488,12 @@ class Executor:
         T.fuse = self._bn_fusion_map()
         if self.bf16:
             # bf16: the pointwise GEMMs can carry the sums (dl3p_pwconv_bwd_data_bn_bf16, more than 64 rows), the depthwise
-            # kernels cannot.  Opt-in: measured slower than the separate reduce pass (the epilogue meets z in 8-byte pieces:
-            # MobileNetV2 513x513 batch 16 12.37 against 11.83 ms, MobileNetV3-Large 1024x2048 batch 1 6.92 against 6.86)
-            T.fuse = {c: b for c, b in T.fuse.items() if c.kind == 'conv_pw' and self._rows(c) > 64
-                      and os.environ.get('DL3P_BF16_FUSE_BN_BWD', '0') == '1'}
+            # kernels cannot.  Opt-in (the `bf16_fuse_bn_bwd` row of exec_options.py): measured slower than the separate reduce pass
+            # (the epilogue meets z in 8-byte pieces)
+            T.fuse = {c: b for c, b in T.fuse.items() if c.kind == 'conv_pw' and self._rows(c) > 64 and self.opts.bf16_fuse_bn_bwd}
         T.stage_off = self._sync_total
         T.readers = self._bn_readers()
         T.bn_of = {id(o.z): o for o in self.g.ops if o.kind == 'bn'}
-        T.alias_ok = os.environ.get('DL3P_GRAD_ALIAS', '1') != '0'
         # BatchNorm -> residual Add -> pointwise conv: the conv's data gradient is the last writer of d/d(Add output), which
         # IS the gradient of the BatchNorm output, so it carries that BatchNorm's backward sums too (no bn_bwd_reduce pass)
         T.fuse_add = self._bn_fusion_through_adds(T.readers) if not self.bf16 else {}
@@ -1533,7 +1501,7 @@ class Executor:
         # reduces them all (dl3p_reduce_rows_batched; 65 reduce launches of 5-13 us each otherwise) -- at the end of
         # backward on one GPU, per gradient bucket under data parallelism (in front of the bucket's all-reduce).  Same
         # per-element arithmetic as the per-layer reduction, whichever way the jobs are grouped.
-        T.batch = os.environ.get('DL3P_BATCHED_WGRAD', '1') != '0'
+        T.batch = self.opts.batched_wgrad
         T.batch_wgrad = T.batch and not T.defer
         if T.batch_wgrad and not self.bf16:
             need = max([self._rows(op) * (op.cout if op.kind == 'conv_pw' else op.c) for op in self.g.ops
@@ -1752,7 +1720,7 @@ class Executor:
         M = self.N * out.H * out.W
         if op.x.tensor.requires_grad or op.x.tensor.root.requires_grad:
             xb = T.bn_of.get(id(op.x.tensor)) if op.x.bn is not None else None
-            if (T.alias_ok and xb is not None and float(op.rate) == 0.0 and getattr(op.x, 'view_grad', None) is None
+            if (self.opts.grad_alias and xb is not None and float(op.rate) == 0.0 and getattr(op.x, 'view_grad', None) is None
                     and op.x.tensor.C == out.C and T.readers.get(xb) == {op} and op.x.tensor.id not in T.written
                     and (op.x.tensor.base is None or op.x.tensor.base.id not in T.written)):
                 # a residual Add hands its gradient to the BatchNorm branch unchanged: that BatchNorm's backward
@@ -1766,7 +1734,7 @@ class Executor:
         if op.r is not None and (op.r.tensor.requires_grad or op.r.tensor.root.requires_grad):
             rt = op.r.tensor
             rb = T.bn_of.get(id(rt)) if op.r.bn is not None else None
-            fresh = (T.alias_ok and getattr(op.r, 'view_grad', None) is None and rt.C == out.C
+            fresh = (self.opts.grad_alias and getattr(op.r, 'view_grad', None) is None and rt.C == out.C
                      and rt.id not in T.written and (rt.base is None or rt.base.id not in T.written))
             if fresh and rb is not None and T.readers.get(rb) == {op}:
                 T.galias[rt.id] = (gt, ldt)        # the other branch is a BatchNorm too (Xception shortcut)
@@ -1823,7 +1791,7 @@ class Executor:
         at, bt = op.x.tensor, op.r.tensor
         if at.requires_grad or at.root.requires_grad:
             xb = T.bn_of.get(id(at)) if op.x.bn is not None else None
-            if (T.alias_ok and xb is not None and getattr(op.x, 'view_grad', None) is None and at.C == out.C
+            if (self.opts.grad_alias and xb is not None and getattr(op.x, 'view_grad', None) is None and at.C == out.C
                     and T.readers.get(xb) == {op} and at.id not in T.written and (at.base is None or at.base.id not in T.written)):
                 T.galias[at.id] = (gt, ldt)
                 T.written.add(at.id)
@@ -1948,8 +1916,7 @@ class Executor:
 
     def _use_sb(self, op, fwd, stats):
         """does this pointwise conv run on the split-bf16 GEMM (forward / data-gradient role)?  Only where the tiled kernel
-        serves the shape and the product is compute-bound enough for the bf16 pipe to pay: reduction length and output width from
-        DL3P_SPLIT_MIN_K / DL3P_SPLIT_MIN_N (measured: scripts/micro/sb_gemm.py)"""
+        serves the shape and the product is compute-bound enough for the bf16 pipe to pay (the `split_min_*` rows of exec_options.py)"""
         st = self.store
         if st.Sb is None or op not in st.sb_shape_f:
             return False
@@ -1958,17 +1925,16 @@ class Executor:
         # where it pays (profiles/r03_split_gemm.txt): many output tiles and a moderate reduction length.  Few-row layers with a
         # long reduction (Xception's 4356 x 2048 -> 256) and narrow outputs (576 -> 96) are faster on the fp32-input MFMA kernel;
         # the data gradient with the fused BatchNorm sums only wins on the long decoder layers.
-        env = os.environ.get
+        o = self.opts
         role = (1 if stats else 0) if fwd else (3 if stats else 2)
-        pinned = any(k in os.environ for k in ('DL3P_SPLIT_MIN_K', 'DL3P_SPLIT_MIN_N', 'DL3P_SPLIT_MIN_ROWS', 'DL3P_SPLIT_MIN_ROWS_BN'))
         # the measured verdict for this exact launch where there is one (csrc/sb_tuned.h, scripts/tune_split.py), else the rule
-        pays = -1 if pinned else self.L.pwconv_sb_pays(role, M, kred, nout)
+        pays = -1 if o.split_pinned else self.L.pwconv_sb_pays(role, M, kred, nout)
         if pays == 0:
             return False
         if pays < 0:
-            if kred < int(env('DL3P_SPLIT_MIN_K', '128')) or nout < int(env('DL3P_SPLIT_MIN_N', '128')):
-                return False
-            if M < int(env('DL3P_SPLIT_MIN_ROWS', '16384')) or (not fwd and stats and M < int(env('DL3P_SPLIT_MIN_ROWS_BN', '60000'))):
+            k, n, rows, rows_bn = (d if v is None else v for v, d in ((o.split_min_k, 128), (o.split_min_n, 128),
+                                                                       (o.split_min_rows, 16384), (o.split_min_rows_bn, 60000)))
+            if kred < k or nout < n or M < rows or (not fwd and stats and M < rows_bn):
                 return False
         if not self.L.pwconv_sb_supported(role, M, kred, nout):
             return False
@@ -1998,7 +1964,7 @@ class Executor:
         pointwise or depthwise conv: its data-gradient kernel is then the last writer of the gradient
         of the BN output and emits the BN-backward partial sums itself (dl3p_pwconv_bwd_data_bn / dl3p_dwconv2d_bwd_data_bn); the BN's
         finalize + apply are issued right behind it and the separate reduce pass over (g, z) disappears."""
-        if os.environ.get('DL3P_FUSE_BN_BWD', '1') == '0':
+        if self.opts.fuse_bn_bwd == 'off':
             return {}
         cons = {}
         for op in self.g.ops:
@@ -2016,7 +1982,7 @@ class Executor:
             op, slot, v = lst[0]
             if any(getattr(vv, 'view_grad', None) is not None for _, _, vv in lst):
                 continue
-            if len(lst) > 1 and os.environ.get('DL3P_FUSE_BN_BWD', '1') == '1single':
+            if len(lst) > 1 and self.opts.fuse_bn_bwd == 'single':
                 continue
             if slot == 'x' and op.kind in ('conv_pw', 'conv_dw') and v.tensor is bn.z and op not in fuse:
                 fuse[op] = bn_ops[bn]
@@ -2026,7 +1992,7 @@ class Executor:
         """{pointwise conv op: 'bn' op} for BatchNorm -> Add (BatchNorm branch + another branch, no dropout) -> conv, where the
         conv is the FIRST consumer of the Add's output in graph order (so its data gradient is issued last in backward and
         completes d/d(Add output) = d/d(BatchNorm output)), reads it plain, and the Add is the BatchNorm's only reader"""
-        if os.environ.get('DL3P_FUSE_BN_BWD', '1') == '0':
+        if self.opts.fuse_bn_bwd == 'off':
             return {}
         bn_of = {id(o.z): o for o in self.g.ops if o.kind == 'bn'}
         first = {}                        # tensor id -> first op (graph order) that reads it
@@ -2133,7 +2099,7 @@ class Executor:
         (dl3p_pwconv_bwd_data_sb_apply: the long decoder layers on the row-stationary split GEMM; fp32, local statistics)"""
         conv = getattr(bn_op, 'producer', None)
         if (self.bf16 or self.sync_bn or self.dist is not None or conv is None or conv.kind != 'conv_pw' or conv.out is not bn_op.z
-                or os.environ.get('DL3P_FOLD_APPLY', '1') == '0' or os.environ.get('DL3P_FOLD_APPLY_DGRAD', '1') == '0'
+                or self.opts.fold_apply == 'off' or not self.opts.fold_apply_dgrad
                 or conv in self._irb_expand):
             return False
         xt = conv.x.tensor
@@ -2158,7 +2124,7 @@ class Executor:
         conv = getattr(bn_op, 'producer', None)
         if (self.bf16 or self.sync_bn or self.dist is not None or conv is None or conv.kind not in ('conv_pw', 'conv_dw', 'conv_dense')
                 or conv.out is not bn_op.z or not conv.layer.trainable or not self._bt.batch_wgrad
-                or os.environ.get('DL3P_FOLD_APPLY', '1') == '0' or not self._slab_bytes(conv)):
+                or self.opts.fold_apply == 'off' or not self._slab_bytes(conv)):
             return False
         if conv in self._irb_dw or conv in self._irb_expand:
             return False
@@ -2166,16 +2132,12 @@ class Executor:
             # the direct stem kernel (3 input channels, stride 2) whose input needs no gradient: dl3p_stem_conv_bwd_weight_slabs_bn
             xt = conv.x.tensor
             return bool(self._route(conv) == R_STEM and not (xt.requires_grad or xt.root.requires_grad)
-                        and os.environ.get('DL3P_FOLD_APPLY_STEM', '1') != '0')
+                        and self.opts.fold_apply_stem)
         M = self.N * conv.Ho * conv.Wo
         if conv.kind == 'conv_dw':
-            # measured on MI355X: the depthwise window kernel with the fold takes as much longer as the apply pass it
-            # replaces took (MobileNetV2 step 14.12 ms against 14.05 with the pointwise folds alone, 14.25 without any)
-            # ... on every depthwise conv.  On the two 129 x 129 decoder layers alone (324 / 272 MB tensors: the apply pass is
-            # 174 / 136 us of pure traffic) the folded weight gradient is 319 / 236 us against 329 / 264 for the pair it replaces
-            # (round 5, same box): those two take it; DL3P_FOLD_APPLY=2 folds every depthwise conv
-            big = M * conv.c * 4 >= int(os.environ.get('DL3P_FOLD_APPLY_DW_MIN_BYTES', str(250 << 20)))
-            if os.environ.get('DL3P_FOLD_APPLY', '1') != '2' and not big:
+            # (measured: it pays on the two 129 x 129 decoder layers only -- the `fold_apply_dw_min_bytes` row of exec_options.py)
+            big = M * conv.c * 4 >= self.opts.fold_apply_dw_min_bytes
+            if self.opts.fold_apply != 'every_dw' and not big:
                 return False
             xt = conv.x.tensor
             return bool(self.L.dwconv2d_bwd_weight_bn_supported(self.N, xt.H, xt.W, conv.c, conv.k, conv.stride, conv.rate,
@@ -2405,9 +2367,8 @@ class Executor:
         torch.cuda.synchronize()
         self.L.set_option(b'split_wgrad', self._split_wgrad)      # (the capture re-issues every C call)
         # the trace already ran every kernel once; undo its side effects on the step counter only
-        in_graph = os.environ.get('DL3P_COLLECTIVES_IN_GRAPH', '1') != '0'     # 0: force the segmented fallback
         for plan in ([self.fwd, self.bwd, self.opt] if self.training else [self.fwd]):
-            plan.capture(collectives_in_graph=in_graph)
+            plan.capture(collectives_in_graph=self.opts.collectives_in_graph)      # (off: force the segmented fallback)
         self.graphed = True
 
     def _sb_sync(self):
@@ -2510,7 +2471,7 @@ class Executor:
             plan = (ctypes.c_int * 6)()
             xt = op.x.tensor
             self.L.dw_plan_query(0, self.N, xt.H, xt.W, op.c, op.k, op.stride, op.rate, op.pad_t, op.pad_l, op.Ho, op.Wo, plan)
-            if op.k == 3 and plan[0] in (1, 2) and os.environ.get('DL3P_BF16_DW_WINDOW', '1') != '0':
+            if op.k == 3 and plan[0] in (1, 2) and self.opts.bf16_dw_window:
                 kname = 'dwb_fwd_seg<3, %d, %d' % (plan[1] if plan[0] == 1 else 2, op.stride)
         probe = Probe(op, kname)
         self.fwd.probe(name, probe)
