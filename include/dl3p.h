@@ -960,6 +960,33 @@ int dl3p_nearest_argmax_confusion(const float* z, int ldz, const float* labels, 
 int dl3p_nearest_class_counts(const float* z, int ldz, const float* labels, int32_t* counts, int N, int h, int w, int C, int H,
                               int W, void* stream);
 
+/* ---------------------------------------------------------------- inference front end (deeplab.py, csrc/infer_io.hip)
+ * The byte-level steps around the network in DeepLab.segment_image: preprocess_image's resize in front (common/data_utils.py:436-454),
+ * mask_resize and visualize_segmentation's colour map and alpha composite behind (:457-477, common/utils.py:221-263, 305-315).
+ * No float64 on the device: the host computes the tables (augment.pil_resize_tables, inference.overlay_tables) and uploads them.
+ * dl3p_pil_resize_u8: PIL's Image.resize((W, H), Image.BICUBIC) of N 8-bit RGB images (h, w) -> (H, W), PINNED against Pillow
+ * (tests/golden/make_pil_bicubic.py and live): a horizontal pass (only if w != W), its result rounded to bytes, then a vertical pass
+ * (only if h != H); equal sizes give a copy.  One pass: acc = 2^21 + sum_{x < cnt} src[min + x] k[x], out = clamp(acc >> 22, 0, 255)
+ * (int32, arithmetic shift).  tables: the horizontal axis' {min[W], cnt[W], k[W][kx]} if kx > 0, then the vertical axis' {min[H],
+ * cnt[H], k[H][ky]} if ky > 0, all int32 on the device, k in 22-bit fixed point; kx / ky = coefficients per output sample, 0 for the
+ * pass that is skipped, at most 65 (a shrink by up to 16).  Source rows are img_pitch bytes apart and image n starts n * h rows after
+ * image 0; `out` is dense, so it may point at a slot of a batch.  workspace: dl3p_pil_resize_workspace() bytes on the device, 4-byte
+ * aligned (the byte intermediate between the passes; 0 when at most one pass runs, workspace may then be NULL).
+ * dl3p_mask_overlay_u8: for every pixel (y, x) of N frames (h0, w0): m = pred[n][ny[y]][nx[x]] from the int32 mask (H, W) that
+ * dl3p_argmax_confusion / dl3p_nearest_argmax_confusion leave; mask_out = (uint8) m, which is mask_resize (cv2.INTER_NEAREST; nx / ny
+ * as in dl3p_aug_resize_u8, min(floor(d * (1.0 / (dst / src))), src - 1)); d = m, or n_valid if n_valid > 0 and m > n_valid - 1 (the
+ * "invalid" display class); overlay_out = (img * (256 - alpha) + colormap[d] * alpha + 128) >> 8 per channel, alpha = rint(overlay *
+ * 256) in 0..256.  This blend is the project's own integer rule for imshow(image); imshow(mask, alpha=overlay) at the frame's own
+ * resolution (the reference renders through matplotlib onto a canvas with a legend).  tables: nx[w0], ny[h0] ints on the device;
+ * colormap: 256 x 3 bytes on the device (create_pascal_label_colormap).  mask_out or overlay_out may be NULL (img and colormap are
+ * read only for the overlay). */
+size_t dl3p_pil_resize_workspace(int N, int h, int w, int H, int W);
+int dl3p_pil_resize_u8(const unsigned char* img, int img_pitch, unsigned char* out, unsigned char* workspace, size_t workspace_bytes,
+                       const int* tables, int kx, int ky, int N, int h, int w, int H, int W, void* stream);
+int dl3p_mask_overlay_u8(const int* pred, const unsigned char* img, unsigned char* mask_out, unsigned char* overlay_out,
+                         const int* tables, const unsigned char* colormap, int n_valid, int alpha, int N, int H, int W, int h0, int w0,
+                         void* stream);
+
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP
  * events (hipExtLaunchKernelGGL start/stop events on the launch stream) stored in slot i (0 <= i < 4096);

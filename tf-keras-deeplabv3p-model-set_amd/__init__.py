@@ -11,10 +11,11 @@ from .model import (get_deeplabv3p_model, get_unet_model, get_fast_scnn_model, d
                     AverageModelCheckpoint)
 
 from .data import SegmentationGenerator  # noqa: F401,E402
+from .inference import DeepLab  # noqa: F401,E402
 from . import mixed_precision  # noqa: F401,E402
 from . import watchdog  # noqa: F401,E402
 
 __all__ = ['get_deeplabv3p_model', 'get_unet_model', 'get_fast_scnn_model', 'deeplab_model_map', 'DeeplabModel', 'SGD', 'Adam', 'RMSprop', 'get_optimizer',
            'SparseCategoricalCrossEntropy', 'WeightedSparseCategoricalCrossEntropy', 'SparseSoftmaxFocalLoss',
            'miou_from_confusion', 'Jaccard', 'jaccard_from_counts', 'EvalCallBack', 'MovingAverage', 'SWA', 'Lookahead',
-           'AverageModelCheckpoint', 'SegmentationGenerator', 'mixed_precision']
+           'AverageModelCheckpoint', 'SegmentationGenerator', 'mixed_precision', 'DeepLab']

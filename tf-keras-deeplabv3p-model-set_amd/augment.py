@@ -16,8 +16,14 @@ out in DESIGN.md section 7 and restated in NumPy by tests/cv_rules.py, which is 
 parts (the inverted rotation matrix, the resize scales) are evaluated here, on the host, into small integer tables that are uploaded
 with the call (warp_tables, resize_tables).
 
+pil_resize is the inference front end's resize (common/data_utils.py:436-454, preprocess_image): PIL's Image.resize(size, BICUBIC),
+Pillow's antialiased 8-bit resampler restated in integers and PINNED against Pillow (tests/pil_rules.py, tests/golden/pil_bicubic.npz);
+its float64 filter weights become 22-bit fixed-point tables on the host (pil_resize_tables).
+
 Not here: the decode (PIL, on the host: data.py) and warpAffine / resize with any other interpolation than the reference's.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -265,6 +271,12 @@ def random_histeq(images, size=8, prob=.2):
     return clahe(images, flags)
 
 
+def nearest_axis(dst, src):
+    """cv2.INTER_NEAREST: the source index of every destination index, min(floor(d * scale), src - 1), scale = 1 / (dst / src)"""
+    scale = 1.0 / (float(dst) / src)
+    return np.minimum(np.floor(np.arange(dst, dtype=np.float64) * scale), src - 1)
+
+
 def _linear_axis(dst, src, zero_at_edges):
     scale = 1.0 / (float(dst) / src)
     f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
@@ -279,8 +291,7 @@ def _linear_axis(dst, src, zero_at_edges):
         s, s1 = np.clip(s, 0, src - 1), np.clip(s + 1, 0, src - 1)
     w0 = np.clip(np.rint((np.float32(1) - f) * np.float32(2048)), -32768, 32767)
     w1 = np.clip(np.rint(f * np.float32(2048)), -32768, 32767)
-    nearest = np.minimum(np.floor(np.arange(dst, dtype=np.float64) * scale), src - 1)
-    return [s, s1, w0, w1, nearest]
+    return [s, s1, w0, w1, nearest_axis(dst, src)]
 
 
 def resize_tables(h, w, H, W):
@@ -316,3 +327,85 @@ def resize(images, labels, shape, out=None):
     lib().aug_resize_u8(images.data_ptr(), _rows_of(images, 3 * w), oi.data_ptr(), labels.data_ptr(), _rows_of(labels, w), ol.data_ptr(),
                         tab.data_ptr(), N, h, w, H, W, _stream())
     return oi, ol
+
+
+# ------------------------------------------------------------------------------------------------ PIL Image.resize (BICUBIC)
+PIL_MAX_KSIZE = 65          # coefficients per output sample the kernel holds: a shrink by up to 16
+
+
+def _bicubic(v):
+    """Pillow's bicubic_filter (a = -0.5) on a float64 array, each operation rounded once in the order Pillow's C evaluates it"""
+    a = -0.5
+    t = np.abs(v)
+    near = ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    far = (((t - 5) * t + 8) * t - 4) * a
+    return np.where(t < 1.0, near, np.where(t < 2.0, far, 0.0))
+
+
+def _pil_axis(src, dst):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for one axis -> (min[dst], cnt[dst], k[dst][ksize]) int32"""
+    scale = float(src) / float(dst)
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    if ksize > PIL_MAX_KSIZE:
+        raise ValueError('pil_resize: %d -> %d needs %d coefficients per sample; the kernel holds %d (a shrink by up to 16)'
+                         % (src, dst, ksize, PIL_MAX_KSIZE))
+    ss = 1.0 / fs
+    center = (np.arange(dst, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum((center - support + 0.5).astype(np.int64), 0)              # (int) truncates towards zero, like astype
+    cnt = np.minimum((center + support + 0.5).astype(np.int64), src) - lo
+    tap = np.arange(ksize, dtype=np.int64)
+    live = tap[None, :] < cnt[:, None]
+    w = np.where(live, _bicubic(((tap[None, :] + lo[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss), 0.0)
+    ww = np.zeros(dst, np.float64)
+    for t in range(ksize):                                                      # Pillow sums in tap order (np.sum would pair up)
+        ww = ww + w[:, t]
+    w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+    k = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << 22))
+    return lo.astype(np.int32), cnt.astype(np.int32), np.where(live, k, 0).astype(np.int32)
+
+
+def pil_resize_tables(h, w, H, W, filter='bicubic'):
+    """the integers dl3p_pil_resize_u8 takes for Image.resize((W, H), BICUBIC) of an (h, w) image -> (tables, kx, ky): per axis
+    {min[out], cnt[out], k[out][ksize]} -- first source sample, number of taps, and Pillow's coefficients in 22-bit fixed point from
+    scale = in / out in float64 -- the horizontal axis first; an axis that keeps its length has no pass, no section and ksize 0"""
+    if filter != 'bicubic':
+        raise ValueError("pil_resize_tables: only 'bicubic' is built (got %r)" % (filter,))
+    parts, ks = [], []
+    for src, dst in ((w, W), (h, H)):
+        if src == dst:
+            ks.append(0)
+            continue
+        lo, cnt, k = _pil_axis(src, dst)
+        parts += [lo, cnt, k.reshape(-1)]
+        ks.append(k.shape[1])
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int32)), ks[0], ks[1]
+
+
+@functools.lru_cache(maxsize=8)
+def _pil_tables_on(device, h, w, H, W):
+    """pil_resize_tables on `device`; kept per size pair, so a stream of equal frames builds and uploads its tables once"""
+    tables, kx, ky = pil_resize_tables(h, w, H, W)
+    return (torch.as_tensor(tables).to(device) if tables.size else None), kx, ky
+
+
+def pil_resize(images, shape, out=None):
+    """PIL's Image.fromarray(image).resize(shape[::-1], Image.BICUBIC) for a batch (N, h, w, 3) of CUDA uint8 images, bit for bit;
+    shape = (H, W).  The input may be a row-pitched view (a crop window).  out: a dense uint8 tensor of N * H * W * 3 bytes to write
+    into, e.g. one slot of a batch; made here when None.  Raises ValueError for a shrink by more than 16 along either axis."""
+    N, h, w, _ = images.shape
+    H, W = int(shape[0]), int(shape[1])
+    if H < 1 or W < 1:
+        raise ValueError('pil_resize: the output size must be at least 1 x 1 (got %r)' % ((H, W),))
+    dev = images.device
+    tab, kx, ky = _pil_tables_on(dev, h, w, H, W)
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == N * H * W * 3
+    L = lib()
+    nws = L.pil_resize_workspace(N, h, w, H, W)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    L.pil_resize_u8(images.data_ptr(), _rows_of(images, 3 * w), out.data_ptr(), ws.data_ptr() if nws else None, nws,
+                    tab.data_ptr() if tab is not None else None, kx, ky, N, h, w, H, W, _stream())
+    return out

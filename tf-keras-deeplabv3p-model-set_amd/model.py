@@ -764,9 +764,12 @@ class DeeplabModel:
         """class ids (B,H,W) int32 = np.argmax(predict(x), -1) (eval.py:33-36, deeplab.py:97-99) taken on the device: the
         mask is 1/84 of the bytes of the 21-class probability tensor"""
         import torch
-        x = np.asarray(x[0] if isinstance(x, (list, tuple)) else x)
-        if x.dtype != np.uint8:
-            x = x.astype(np.float32, copy=False)
+        if isinstance(x, (list, tuple)):
+            x = x[0]
+        if not _on_device_u8(x):                # (CUDA uint8 tensors go to set_inputs as they are)
+            x = np.asarray(x)
+            if x.dtype != np.uint8:
+                x = x.astype(np.float32, copy=False)
         B = x.shape[0]
         ex = self._executor(B, False)
         ex.set_inputs(x)
