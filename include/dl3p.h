@@ -546,6 +546,22 @@ int dl3p_upsample_softmax_loss(const float* z, int ldz, const float* labels, int
  * integer atomics, order-independent).  pred_mask, or labels + confusion, may be NULL. */
 int dl3p_argmax_confusion(const float* z, int ldz, const float* labels, int32_t* pred_mask,
                           unsigned long long* confusion, int N, int h, int w, int C, int H, int W, void* stream);
+/* Multi-scale / mirrored evaluation head (DeepLab's evaluation protocol: class probabilities of several input scales and of the
+ * mirrored image averaged before the argmax; the reference repository has no counterpart).  One call adds one scale's passes into a
+ * running fp32 sum acc (N,H,W,ld_acc) without a per-pass probability tensor:
+ *   acc_out = (acc_in + weight * softmax(U)) + weight * softmax(Um)[.., W-1-x, :]
+ * U / Um = the bilinear upsampling (the rule of dl3p_resize_bilinear_fwd) of z / z_mirror, fp32 logit maps (N,h,w,.) with row
+ * strides ldz / ldzm (>= C, multiples of 4); z_mirror holds the logits of the frame reversed along x.  Either map may be NULL (its
+ * term is left out), not both.  acc_in NULL starts from 0; acc_out NULL writes nothing; acc_in == acc_out is allowed; ld_acc >= C
+ * and a multiple of 4, channels C .. roundup4(C)-1 are written as 0, channels beyond stay untouched.  pred_mask, labels and confusion
+ * are those of dl3p_argmax_confusion, taken on the sum as it stands after this call, written out or not.  The additions happen in
+ * the order written (no contraction), so a paired call equals a plain-only call followed by a mirror-only call bit for bit.
+ * DL3P_EINVAL before any launch: C outside [1, 256], h > H or w > W, a base that is not 16-byte aligned, a bad stride, no output
+ * requested, labels without confusion or the reverse.  Offsets are 64-bit. */
+int dl3p_tta_accumulate(const float* z, int ldz, const float* z_mirror, int ldzm, int h, int w, float weight,
+                        const float* acc_in, float* acc_out, int ld_acc,
+                        const float* labels, int32_t* pred_mask, unsigned long long* confusion,
+                        int N, int C, int H, int W, void* stream);
 /* Training metrics (deeplabv3p/metrics.py:20-46, train.py:140): per image n and class c,
  * counts[n][0][c] = |label == c and pred == c|, counts[n][1][c] = |label == c|, counts[n][2][c] = |pred == c| (over all
  * pixels, ignored labels included), pred = argmax of the upsampled logits.  int32 [N][3][C], zeroed by the caller. */

@@ -2425,6 +2425,20 @@ class Executor:
                                 None if confusion is None else confusion.data_ptr(), self.N, zt.H, zt.W, self.C, self.H,
                                 self.W, torch.cuda.current_stream().cuda_stream)
 
+    def eval_logits(self):
+        """inference forward up to the head, the body eval_step runs (its cached plan; built here when eval_step has not run yet)
+        -> the low-resolution fp32 logits (N, h, w, Cpad), a view of the executor's own buffer that the next run overwrites:
+        what dl3p_tta_accumulate takes from each pass of a multi-scale evaluation"""
+        assert not self.training
+        if getattr(self, '_eval_plan', None) is None:
+            P = Plan()
+            P.items = list(self.fwd.items[:-1])
+            P.labels = list(self.fwd.labels[:-1])
+            self._eval_plan = P
+        self._sb_sync()
+        self._eval_plan.run()
+        return self.view(self.head.tensor)
+
     def eval_loss_step(self, counts=None):
         """validation step on the device: inference forward, the compiled loss against self.labels (no gradient, no
         probability tensor) and, if asked for, the per-image class counts of the Jaccard metric; -> loss tensor [1]"""

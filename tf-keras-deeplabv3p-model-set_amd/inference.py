@@ -21,7 +21,7 @@ import numpy as np
 
 from . import augment
 from ._lib import lib
-from .model import _on_device_u8, get_deeplabv3p_model, get_fast_scnn_model, get_unet_model
+from .model import _default_tta, _on_device_u8, _tta_check, _tta_run, get_deeplabv3p_model, get_fast_scnn_model, get_unet_model
 
 OVERLAY = 0.7               # visualize_segmentation's default alpha
 
@@ -127,6 +127,10 @@ class DeepLab(object):
         'output_stride': 16,
         'weights_path': os.path.join('weights', 'mobilenetv2_original.h5'),
         'do_crf': False,
+        # DeepLab's multi-scale / mirrored protocol (not the reference's deeplab.py, which predicts one scale): the defaults keep the
+        # single unmirrored pass
+        'scales': (1.0,),
+        'flip': False,
     }
 
     def __init__(self, **kwargs):
@@ -137,6 +141,9 @@ class DeepLab(object):
         self.model_input_shape = tuple(int(v) for v in self.model_input_shape)
         self.class_names = get_classes(self.classes_path)
         self.deeplab_model = self._generate_model()
+        self._tta = not _default_tta(self.scales, self.flip)
+        if self._tta:
+            self.scales = _tta_check(self.deeplab_model, self.scales)
 
     def _generate_model(self):
         num_classes = len(self.class_names)
@@ -162,6 +169,8 @@ class DeepLab(object):
         H, W = self.model_input_shape
         if tuple(x.shape[1:]) != (H, W, 3):
             raise ValueError('the model takes (N, %d, %d, 3) images, got %r' % (H, W, tuple(x.shape)))
+        if self._tta:                           # the mask of the last dl3p_tta_accumulate launch; the frames are bytes then
+            return _tta_run(self.deeplab_model, x, self.scales, self.flip, want_mask=True)[1]
         ex = self.deeplab_model._executor(N, False)
         ex.set_inputs(x)
         pred = torch.empty(N * H * W, dtype=torch.int32, device='cuda')

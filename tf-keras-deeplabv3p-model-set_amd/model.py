@@ -1058,6 +1058,187 @@ def _evaluate_miou(self, gen, steps=None, class_names=None, verbose=0):
 DeeplabModel.evaluate_miou = _evaluate_miou
 
 
+# ---- multi-scale / mirrored evaluation ----------------------------------------------------------------------------------
+# DeepLab's evaluation protocol (the published mIoU figures): the image at several scales, each also mirrored, the class
+# probabilities of all passes averaged at the base resolution before the argmax.  The reference repository evaluates one scale,
+# unmirrored; the semantics below are this project's.  Per scale one dl3p_tta_accumulate launch adds the plain
+# and the mirrored pass into one running sum; the last launch writes no sum and leaves the mask / the confusion counters.
+def tta_size(n, s):
+    """DeepLab's crop-size rule for a side of n pixels at scale s: int((n - 1) * s + 1.0) in float64 (513 -> 257, 385, 641, 769, 897
+    for 0.5 .. 1.75; s = 1 gives n)"""
+    return int((int(n) - 1) * float(s) + 1.0)
+
+
+def _default_tta(scales, flip):
+    try:
+        return not flip and tuple(float(s) for s in scales) == (1.0,)
+    except TypeError:
+        return False
+
+
+def _tta_check(self, scales):
+    """ValueError for what the multi-scale evaluation does not serve -> the scales as a tuple of floats"""
+    if getattr(self, '_factory', None) is None:
+        raise ValueError("multi-scale / mirrored evaluation is built for get_deeplabv3p_model models only, not for '%s' from "
+                         "get_unet_model / get_fast_scnn_model" % (self.model_type,))
+    scales = tuple(float(s) for s in scales)
+    if not scales:
+        raise ValueError('scales must name at least one scale (got an empty sequence)')
+    for s in scales:
+        if not s > 0:
+            raise ValueError('scales must be positive (got %r)' % (s,))
+    return scales
+
+
+def _tta_siblings(self, scales):
+    """one inference model per scale, in the order given: this model for a scale that keeps its input shape, otherwise a sibling from
+    the same factory with this model's arguments at (tta_size(H, s), tta_size(W, s)).  Siblings are cached per shape and built only
+    when absent; every call refreshes their weights from this model's parameter store"""
+    import contextlib
+    import io
+    from . import mixed_precision
+    scales = _tta_check(self, scales)
+    H, W = self.input_shape_hw
+    cache = self.__dict__.setdefault('_tta_cache', {})
+    out = []
+    for s in scales:
+        shape = (tta_size(H, s), tta_size(W, s))
+        if shape == (H, W):
+            out.append(self)
+            continue
+        if shape not in cache:
+            if min(shape) < 1:
+                raise ValueError('scale %r gives the input shape %r' % (s, shape))
+            f = self._factory
+            policy = mixed_precision._GLOBAL
+            mixed_precision._GLOBAL = 'mixed_bfloat16' if self.bf16 else 'float32'      # the policy this model was built under
+            try:
+                with contextlib.redirect_stdout(io.StringIO()):
+                    cache[shape] = get_deeplabv3p_model(f['model_type'], self.num_classes, shape, f['output_stride'], freeze_level=0,
+                                                        weights_path=None, training=False, seed=self.seed,
+                                                        bn_moving_variance=f['bn_moving_variance'])
+            except ValueError as e:
+                raise ValueError("scale %r: model type '%s' cannot be built at input shape %r: %s" % (s, self.model_type, shape, e))
+            finally:
+                mixed_precision._GLOBAL = policy
+        out.append(cache[shape])
+    store = self._ensure_store()
+    for sib in {id(m): m for m in out if m is not self}.values():
+        st = sib._ensure_store()
+        same = st.total == store.total and len(st.params) == len(store.params) and all(
+            a.dev_shape == b.dev_shape and st.offset[a] == store.offset[b] for a, b in zip(st.params, store.params))
+        assert same, 'a sibling at another input shape has the same parameters in the same layout'
+        if same:
+            st.P.copy_(store.P)             # device to device
+            st.transpose()
+        else:
+            sib.set_weights(self.get_weights())
+    return out
+
+
+def _tta_frames(self, frames_u8, check_only=False):
+    """uint8 frames (B,H,W,3) at the model's input shape, host or device -> a dense CUDA uint8 tensor"""
+    import torch
+    dt = getattr(frames_u8, 'dtype', None)
+    if dt not in (np.uint8, torch.uint8):
+        raise ValueError('multi-scale / mirrored evaluation takes uint8 frames (they are resized as bytes, like Pillow does); '
+                         'got dtype %r' % (dt,))
+    H, W = self.input_shape_hw
+    if tuple(frames_u8.shape[1:]) != (H, W, 3):
+        raise ValueError('the model takes (B, %d, %d, 3) frames, got %r' % (H, W, tuple(frames_u8.shape)))
+    if check_only:
+        return None
+    if not isinstance(frames_u8, torch.Tensor):
+        frames_u8 = torch.from_numpy(np.ascontiguousarray(frames_u8))
+    return frames_u8.cuda(non_blocking=True).contiguous()
+
+
+def _tta_run(self, frames_u8, scales, flip, labels=None, confusion=None, want_mask=False, want_sum=False):
+    """the passes of one batch -> (sum (B,H,W,Cpad) or None, mask (B,H,W) int32 or None); labels / confusion: the base executor's
+    label plane and a (C,C) int64 counter tensor that the last launch adds to"""
+    import torch
+    from . import augment, ops
+    from ._lib import lib
+    scales = _tta_check(self, scales)
+    _tta_frames(self, frames_u8, check_only=True)       # (every refusal comes before the first device call)
+    models = _tta_siblings(self, scales)
+    frames = _tta_frames(self, frames_u8)
+    B = int(frames.shape[0])
+    H, W = self.input_shape_hw
+    C = self.num_classes
+    weight = 1.0 / (len(scales) * (2 if flip else 1))
+    ones = torch.ones(B, dtype=torch.int32, device=frames.device) if flip else None      # flags: bit 0 = mirror along x
+    acc = pred = None
+    for i, m in enumerate(models):
+        hs, ws = m.input_shape_hw
+        x = frames if m is self else augment.pil_resize(frames, (hs, ws))
+        ex = m._executor(B, False)
+        ex.set_inputs(x)
+        z, zm = ex.eval_logits(), None
+        if flip:
+            z = z.clone()                       # (the mirrored pass reuses the executor's buffer)
+            xm = torch.empty_like(x)
+            lib().aug_flip_crop_u8(x.data_ptr(), xm.data_ptr(), None, None, ones.data_ptr(), None, B, hs, ws, hs, ws,
+                                   torch.cuda.current_stream().cuda_stream)
+            ex.set_inputs(xm)
+            zm = ex.eval_logits()
+        last = i == len(models) - 1
+        acc, p, _ = ops.tta_accumulate(z, zm, C, H, W, weight, acc=acc, write=(not last) or want_sum,
+                                       labels=labels if last else None, confusion=confusion if last else None,
+                                       want_mask=want_mask and last)
+        pred = p if last else pred
+    return acc, pred
+
+
+def _predict_tta(self, frames_u8, scales=(1.0,), flip=False):
+    """mean class probabilities over the passes of DeepLab's multi-scale / mirrored protocol: frames_u8 (B,H,W,3) uint8 at the model's
+    input shape, on the host or the device -> (B,H,W,C) float32, (B,H*W,C) for a training-shaped model"""
+    acc, _ = _tta_run(self, frames_u8, scales, flip, want_sum=True)
+    H, W = self.input_shape_hw
+    p = acc[..., :self.num_classes].cpu().numpy()
+    return p.reshape(p.shape[0], H * W, self.num_classes) if self.flatten_output else p
+
+
+def _evaluate_miou_tta(self, gen, steps=None, class_names=None, verbose=0, *, scales=(1.0,), flip=False):
+    """_evaluate_miou, and with other `scales` / `flip` than the defaults DeepLab's multi-scale / mirrored protocol (not the reference
+    repository's: eval.py evaluates one scale): per batch every pass's logits are added as probabilities into one running sum on the
+    device and the last launch counts against the labels; only the C x C counters come back.  The generator then yields uint8 images"""
+    if _default_tta(scales, flip):
+        return _evaluate_miou(self, gen, steps, class_names, verbose)
+    import torch
+    scales = _tta_check(self, scales)
+    n = steps or len(gen)
+    C = self.num_classes
+    cm = None
+    for i in range(n):
+        batch = gen[i]
+        x, y = batch[0], batch[1]
+        if not _on_device_u8(x):
+            x = np.asarray(x)
+        _tta_frames(self, x, check_only=True)
+        if cm is None:
+            cm = torch.zeros((C, C), dtype=torch.int64, device='cuda')
+        frames = _tta_frames(self, x)
+        if not _on_device_u8(y):
+            y = np.asarray(y)
+            y = y if y.dtype == np.uint8 else y.astype(np.float32, copy=False)
+        base = self._executor(int(frames.shape[0]), False)
+        base.set_inputs(frames, y)          # the labels of this batch, where the last launch reads them
+        _tta_run(self, frames, scales, flip, labels=base.labels, confusion=cm)
+    res = miou_from_confusion(cm.cpu().numpy() if cm is not None else np.zeros((C, C), np.int64), class_names)
+    if verbose:
+        print('mIoU=%.3f' % (res['mIoU'] * 100))
+        print('FWIoU=%.3f' % (res['FWIoU'] * 100))
+        print('PixelAcc=%.3f' % (res['PixelAcc'] * 100))
+        print('mClassAcc=%.3f' % (res['mClassAcc'] * 100))
+    return res
+
+
+DeeplabModel._tta_siblings = _tta_siblings
+DeeplabModel.predict_tta = _predict_tta
+DeeplabModel.evaluate_miou = _evaluate_miou_tta
+
+
 # model types whose graphs contain ops without a bf16 kernel on the TRAINING path are rejected when the model is built, not at
 # the first train step (ADVICE r02).  Empty since round 3: the data gradient of a dense k x k conv (dl3p_col2im_bf16 behind the
 # GEMM) and max pooling (dl3p_maxpool2d_*_bf16) closed the gap for Xception and ResNet50 -- train.py:37-46 applies the policy to
@@ -1085,6 +1266,8 @@ def get_deeplabv3p_model(model_type, num_classes, model_input_shape, output_stri
         model = _build_model(model_type, num_classes, model_input_shape, output_stride, freeze_level, weights_path, training,
                              use_subpixel, seed, bf16)
         model.graph.bn_moving_variance = model.bn_moving_variance = bn_moving_variance
+        # what _tta_siblings hands the factory again for the same model at another input shape
+        model._factory = {'model_type': model_type, 'output_stride': output_stride, 'bn_moving_variance': bn_moving_variance}
         return model
     finally:
         graph_mod.CHANNEL_ALIGN = 4

@@ -568,6 +568,31 @@ def argmax_confusion(z, C, H, W, labels=None, confusion=None, want_mask=False):
     return pred, (confusion if labels is not None else None)
 
 
+def tta_accumulate(z, z_mirror, C, H, W, weight, acc=None, write=True, labels=None, confusion=None, want_mask=False):
+    """one scale of the multi-scale / mirrored evaluation: acc (N,H,W,Cpad) = (acc + weight * softmax(upsample(z))) + weight *
+    mirror_x(softmax(upsample(z_mirror))); z / z_mirror (N,h,w,Cpad) small logits, either may be None.  acc None starts from 0;
+    write=False leaves the sum unwritten (the last pass: only the mask and / or the counters are wanted).
+    -> (acc or None, pred mask (N,H,W) int32 or None, confusion (C,C) int64 or None) of the sum after this call"""
+    ref = z if z is not None else z_mirror
+    N, h, w, _ = ref.shape
+    zp, ldz = _pl(z)
+    mp, ldm = _pl(z_mirror)
+    cpad = ((C + 3) // 4) * 4
+    out = None
+    if write:
+        out = acc if acc is not None else torch.empty((N, H, W, cpad), dtype=torch.float32, device=ref.device)
+    ap, lda = _pl(acc)
+    op, ldo = _pl(out)
+    if acc is not None and out is not None and lda != ldo:
+        raise Dl3pError('tta_accumulate: one row stride for the sum read and written')
+    pred = torch.empty((N, H, W), dtype=torch.int32, device=ref.device) if want_mask else None
+    if labels is not None and confusion is None:
+        confusion = torch.zeros((C, C), dtype=torch.int64, device=ref.device)
+    lib().tta_accumulate(zp, ldz, mp, ldm, h, w, float(weight), ap, op, lda or ldo, _p(labels), _p(pred),
+                         _p(confusion) if labels is not None else None, N, C, H, W, _stream())
+    return out, pred, (confusion if labels is not None else None)
+
+
 def label_prepare(labels_u8, num_classes, ignore_index=255, adaptive=False, labels_out=None, weights_out=None):
     """uint8 labels (N, P) on the device -> (float32 labels with values above num_classes-1 set to ignore_index,
     float32 'balanced' pixel weights or None): deeplabv3p/data.py:116-145"""
