@@ -556,6 +556,8 @@ class Executor:
         store.step.copy_(snap_step)
         store.opt_step.copy_(snap_ostep)
         self.graphed = False
+        self.steps_run = 0          # train steps so far, counted by the model: it captures the graph on the second (train_on_batch)
+        self._eval_plan = None      # the forward plan without its head (_run_eval_body)
 
     # ---------------------------------------------------------------- buffers
     def _alloc(self):
@@ -2407,18 +2409,22 @@ class Executor:
         self._pin_options()
         self.fwd.run()
 
-    def eval_step(self, confusion, pred=None):
-        """inference forward WITHOUT the probability tensor, then argmax + confusion-matrix accumulation against
-        self.labels on the device (eval.py:33-36, 368-373, 440-443): per batch nothing but the C x C counters changes
-        (predict() writes and downloads N*H*W*C probabilities: 354 MB at batch 16).  confusion: int64 [C*C] tensor."""
+    def _run_eval_body(self):
+        """the inference forward up to the head: what eval_step, eval_logits and eval_loss_step put their own head launch behind"""
         assert not self.training
-        if getattr(self, '_eval_plan', None) is None:
+        if self._eval_plan is None:
             P = Plan()
             P.items = list(self.fwd.items[:-1])            # the body; the last item is the softmax head
             P.labels = list(self.fwd.labels[:-1])
             self._eval_plan = P
         self._sb_sync()
         self._eval_plan.run()
+
+    def eval_step(self, confusion, pred=None):
+        """inference forward WITHOUT the probability tensor, then argmax + confusion-matrix accumulation against
+        self.labels on the device (eval.py:33-36, 368-373, 440-443): per batch nothing but the C x C counters changes
+        (predict() writes and downloads N*H*W*C probabilities: 354 MB at batch 16).  confusion: int64 [C*C] tensor."""
+        self._run_eval_body()
         zt = self.head.tensor
         (self.L.nearest_argmax_confusion if self.nearest_head else self.L.argmax_confusion)(self.tptr(zt), zt.ld, None if confusion is None else self.labels.data_ptr(),
                                 None if pred is None else pred.data_ptr(),
@@ -2429,27 +2435,13 @@ class Executor:
         """inference forward up to the head, the body eval_step runs (its cached plan; built here when eval_step has not run yet)
         -> the low-resolution fp32 logits (N, h, w, Cpad), a view of the executor's own buffer that the next run overwrites:
         what dl3p_tta_accumulate takes from each pass of a multi-scale evaluation"""
-        assert not self.training
-        if getattr(self, '_eval_plan', None) is None:
-            P = Plan()
-            P.items = list(self.fwd.items[:-1])
-            P.labels = list(self.fwd.labels[:-1])
-            self._eval_plan = P
-        self._sb_sync()
-        self._eval_plan.run()
+        self._run_eval_body()
         return self.view(self.head.tensor)
 
     def eval_loss_step(self, counts=None):
         """validation step on the device: inference forward, the compiled loss against self.labels (no gradient, no
         probability tensor) and, if asked for, the per-image class counts of the Jaccard metric; -> loss tensor [1]"""
-        assert not self.training
-        if getattr(self, '_eval_plan', None) is None:
-            P = Plan()
-            P.items = list(self.fwd.items[:-1])
-            P.labels = list(self.fwd.labels[:-1])
-            self._eval_plan = P
-        self._sb_sync()
-        self._eval_plan.run()
+        self._run_eval_body()
         zt, L = self.head.tensor, self.L
         st = torch.cuda.current_stream().cuda_stream
         rows = ctypes.c_int(0)

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import augment
 from ._lib import lib
-from .model import _default_tta, _on_device_u8, _tta_check, _tta_run, get_deeplabv3p_model, get_fast_scnn_model, get_unet_model
+from .model import batch_input, get_deeplabv3p_model, get_fast_scnn_model, get_unet_model, single_pass
 
 OVERLAY = 0.7               # visualize_segmentation's default alpha
 
@@ -141,9 +141,8 @@ class DeepLab(object):
         self.model_input_shape = tuple(int(v) for v in self.model_input_shape)
         self.class_names = get_classes(self.classes_path)
         self.deeplab_model = self._generate_model()
-        self._tta = not _default_tta(self.scales, self.flip)
-        if self._tta:
-            self.scales = _tta_check(self.deeplab_model, self.scales)
+        if not single_pass(self.scales, self.flip):
+            self.scales = self.deeplab_model.tta_scales(self.scales)
 
     def _generate_model(self):
         num_classes = len(self.class_names)
@@ -164,18 +163,10 @@ class DeepLab(object):
 
     def _class_ids(self, x):
         """x: (N, H, W, 3) bytes (CUDA) or normalised float32 (host) at the model's size -> (N, H, W) int32 CUDA class ids"""
-        import torch
-        N = int(x.shape[0])
         H, W = self.model_input_shape
         if tuple(x.shape[1:]) != (H, W, 3):
             raise ValueError('the model takes (N, %d, %d, 3) images, got %r' % (H, W, tuple(x.shape)))
-        if self._tta:                           # the mask of the last dl3p_tta_accumulate launch; the frames are bytes then
-            return _tta_run(self.deeplab_model, x, self.scales, self.flip, want_mask=True)[1]
-        ex = self.deeplab_model._executor(N, False)
-        ex.set_inputs(x)
-        pred = torch.empty(N * H * W, dtype=torch.int32, device='cuda')
-        ex.eval_step(None, pred)
-        return pred.view(N, H, W)
+        return self.deeplab_model.class_ids(x, scales=self.scales, flip=self.flip)      # (multi-scale: the frames are bytes then)
 
     def segment_batch(self, frames):
         """frames (N, h0, w0, 3) uint8, NumPy or a CUDA tensor -> (masks (N, h0, w0), overlays (N, h0, w0, 3)), CUDA uint8 tensors:
@@ -192,10 +183,9 @@ class DeepLab(object):
         (height, width) of the original image -> the class mask at that size, uint8 (height, width) NumPy"""
         if isinstance(image_data, (list, tuple)):
             image_data = image_data[0]
-        x = image_data
-        if not _on_device_u8(x):
-            x = np.asarray(x)
-            x = _device_u8(x) if x.dtype == np.uint8 else x.astype(np.float32, copy=False)
+        x = batch_input(image_data)
+        if isinstance(x, np.ndarray) and x.dtype == np.uint8:       # (bytes on the host go up as bytes)
+            x = _device_u8(x)
         pred = self._class_ids(x)
         masks, _ = _mask_overlay(pred, None, len(self.class_names), (int(image_shape[0]), int(image_shape[1])))
         return masks[0].cpu().numpy()
