@@ -888,6 +888,11 @@ int dl3p_irb_bwd_data(const float* x, int ldx, const float* in_scale, const floa
 int dl3p_irb_set_plan(int ct, int want_waves);
 int dl3p_irb_set_bwd_plan(int want_waves_sums, int want_workgroups_data);
 int dl3p_irb_get_plan(int which);
+/* What a launch WOULD do for this geometry with the knobs as they stand, without launching (as dl3p_dw_plan_query; the launches run
+ * the same planners): which = 0 dl3p_irb_fwd, 1 dl3p_irb_bwd_sums (pass A), 2 dl3p_irb_bwd_data (pass B).  out8 = {channel tiles per
+ * wave (forward, else 0), column segments, row bands, rows (row steps) per band, channel groups, units (waves with work), rows
+ * written (statistic / slab rows), 1 if the shape is supported (else all 0)}. */
+int dl3p_irb_plan_query(int which, int N, int H, int W, int K, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int* out8);
 int dl3p_irb_selftest(float* out128, void* stream);
 
 /* ---------------------------------------------------------------- fused ghost-module forward (csrc/ghost_fwd.hip)

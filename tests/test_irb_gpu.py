@@ -140,6 +140,12 @@ def test_fused_forward(ops, case, ct):
     assert ops.irb_supported((N, H, W, K), C, stride)
     ops.lib().irb_set_plan(ct, 0)
     try:
+        # the channel tiles per wave this launch runs: the ones asked for, or the default where C is no multiple of 16 * ct (C = 144
+        # at ct = 2 falls back to 1) -- 2 where C is a multiple of 32, else 1
+        (Ho, pt, _), (Wo, pl, _) = tf_pad(H, 3, stride), tf_pad(W, 3, stride)
+        plan = (ctypes.c_int * 8)()
+        ops.lib().irb_plan_query(0, N, H, W, K, C, stride, pt, pl, Ho, Wo, plan)
+        assert plan[7] == 1 and plan[0] == (ct if ct and C % (16 * ct) == 0 else (2 if C % 32 == 0 else 1)), list(plan)
         x, xh, w1, wdw, z1 = ref64(d)
         # BatchNorm coefficients from the covariance route
         bn = ops.BNState(C, DEV)

@@ -655,15 +655,42 @@ extern "C" int dl3p_irb_get_plan(int which) {
 }
 static int irb_want_a() { return g_irb_bwd_units_a > 0 ? g_irb_bwd_units_a : 8192; }
 static int irb_want_b() { return g_irb_bwd_units_b > 0 ? g_irb_bwd_units_b : 6144; }
+// the plans of pass A (one wave per 16-channel tile, one row per wave row) and pass B (all channels per wave, one row per workgroup
+// of four) with the knobs as they stand: what the launches, the workspace sizes and dl3p_irb_plan_query all use
+static int irb_plan_sums(IrbParams& p, int N, int H, int W, int C, int stride, int pad_t, int pad_l) {
+  return irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, C / 16, 1, irb_want_a());
+}
+static int irb_plan_data(IrbParams& p, int N, int H, int W, int stride, int pad_t, int pad_l) {
+  return irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, 1, 4, irb_want_b());
+}
 
 extern "C" int dl3p_irb_bwd_supported(int N, int H, int W, int K, int C, int k, int stride, int rate, int pad_t, int pad_l, int Ho,
                                       int Wo) {
   if (!dl3p_irb_supported(N, H, W, K, C, k, stride, rate, pad_t, pad_l, Ho, Wo)) return 0;
   if (!((K == 16 && C == 96) || (K == 24 && C == 144) || (K == 32 && C == 192))) return 0;
   IrbParams p = {};
-  if (irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, C / 16, 1, irb_want_a()) < 0) return 0;
-  if (irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, 1, 4, irb_want_b()) < 0) return 0;
+  if (irb_plan_sums(p, N, H, W, C, stride, pad_t, pad_l) < 0) return 0;
+  if (irb_plan_data(p, N, H, W, stride, pad_t, pad_l) < 0) return 0;
   return 1;
+}
+
+int dl3p_irb_fwd_plan_now(IrbParams& p, int N, int Ho, int Wo, int C, int stride, int* ct);
+extern "C" int dl3p_irb_plan_query(int which, int N, int H, int W, int K, int C, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                                   int* out8) {
+  DL3P_CHECK_ARG(out8 && which >= 0 && which <= 2, "dl3p_irb_plan_query: bad arguments (which=%d)", which);
+  for (int i = 0; i < 8; ++i) out8[i] = 0;
+  const int ok = which == 0 ? dl3p_irb_supported(N, H, W, K, C, 3, stride, 1, pad_t, pad_l, Ho, Wo)
+                            : dl3p_irb_bwd_supported(N, H, W, K, C, 3, stride, 1, pad_t, pad_l, Ho, Wo);
+  if (!ok) return DL3P_OK;
+  IrbParams p = {};
+  int ct = 0;
+  const int rows = which == 0   ? dl3p_irb_fwd_plan_now(p, N, Ho, Wo, C, stride, &ct)
+                   : which == 1 ? irb_plan_sums(p, N, H, W, C, stride, pad_t, pad_l)
+                                : irb_plan_data(p, N, H, W, stride, pad_t, pad_l);
+  if (rows < 0) return DL3P_OK;
+  out8[0] = ct; out8[1] = p.nseg; out8[2] = p.nband; out8[3] = p.band; out8[4] = p.ncg; out8[5] = p.units; out8[6] = rows;
+  out8[7] = 1;
+  return DL3P_OK;
 }
 
 /* bytes of the slab regions: which = 0 depthwise-kernel slabs of dl3p_irb_bwd_sums ([rows][9][C]), 1 expand-kernel slabs of
@@ -671,10 +698,10 @@ extern "C" int dl3p_irb_bwd_supported(int N, int H, int W, int K, int C, int k, 
 extern "C" size_t dl3p_irb_bwd_workspace(int which, int N, int H, int W, int K, int C, int stride, int pad_t, int pad_l) {
   IrbParams p = {};
   if (which == 0) {
-    const int rows = irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, C / 16, 1, irb_want_a());
+    const int rows = irb_plan_sums(p, N, H, W, C, stride, pad_t, pad_l);
     return rows < 0 ? 0 : (size_t)rows * 9 * C * sizeof(float);
   }
-  const int rows = irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, 1, 4, irb_want_b());
+  const int rows = irb_plan_data(p, N, H, W, stride, pad_t, pad_l);
   return rows < 0 ? 0 : (size_t)rows * K * C * sizeof(float);
 }
 
@@ -716,7 +743,7 @@ extern "C" int dl3p_irb_bwd_sums(const float* x, int ldx, const float* in_scale,
   irb_fill(p, x, ldx, in_scale, in_shift, in_act, w1, bn_scale, bn_shift, bn_act, bn_mean, bn_invstd, wdw, dy, lddy, N, H, W, C,
            pad_t, pad_l, Ho, Wo);
   p.slabs = gwdw_slabs; p.partials = bn_partials;
-  const int rows = irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, C / 16, 1, irb_want_a());
+  const int rows = irb_plan_sums(p, N, H, W, C, stride, pad_t, pad_l);
   DL3P_CHECK_ARG((size_t)rows * 9 * C * sizeof(float) <= slab_bytes, "dl3p_irb_bwd_sums: slab region too small");
   if (slab_rows_out) *slab_rows_out = rows;
   hipStream_t st = (hipStream_t)stream;
@@ -766,7 +793,7 @@ extern "C" int dl3p_irb_bwd_data(const float* x, int ldx, const float* in_scale,
            pad_t, pad_l, Ho, Wo);
   p.coef1 = bn_coef; p.slabs = gw1_slabs; p.gx = gx; p.ldgx = ldgx; p.accumulate = accumulate;
   p.z0 = z0; p.ldz0 = ldz0; p.s0 = scale0; p.h0 = shift0; p.act0 = act0; p.mu0 = mean0; p.is0 = invstd0; p.partials0 = partials0;
-  const int rows = irb_bwd_plan(p, N, H, W, stride, pad_t, pad_l, 1, 4, irb_want_b());
+  const int rows = irb_plan_data(p, N, H, W, stride, pad_t, pad_l);
   DL3P_CHECK_ARG((size_t)rows * K * C * sizeof(float) <= slab_bytes, "dl3p_irb_bwd_data: slab region too small");
   if (slab_rows_out) *slab_rows_out = rows;
   hipStream_t st = (hipStream_t)stream;

@@ -520,6 +520,13 @@ static int irb_pick_ct(int C) {
   return C % 32 == 0 ? 2 : 1;
 }
 
+// the forward's plan with the knobs as they stand (what dl3p_irb_fwd launches and dl3p_irb_plan_query reports): -> statistic rows, < 0 if
+// the shape has no plan; *ct = channel tiles per wave
+int dl3p_irb_fwd_plan_now(IrbParams& p, int N, int Ho, int Wo, int C, int stride, int* ct) {
+  *ct = irb_pick_ct(C);
+  return irb_plan(p, N, Ho, Wo, C, stride, *ct, stride == 2 ? 15 : 14, g_irb_waves > 0 ? g_irb_waves : 4096);
+}
+
 extern "C" int dl3p_irb_supported(int N, int H, int W, int K, int C, int k, int stride, int rate, int pad_t, int pad_l, int Ho,
                                   int Wo) {
   if (!(K == 16 || K == 24 || K == 32) || C % 16 != 0 || C < 16 || C > 1024) return 0;
@@ -564,8 +571,8 @@ extern "C" int dl3p_irb_fwd(const float* x, int ldx, const float* in_scale, cons
   p.x = x; p.ldx = ldx; p.xs = in_scale; p.xh = in_shift; p.xact = in_act; p.w1 = w1; p.s1 = bn_scale; p.h1 = bn_shift;
   p.act1 = bn_act; p.wdw = wdw; p.y = y; p.ldy = ldy; p.partials = stat_partials;
   p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = Ho; p.Wo = Wo; p.pad_t = pad_t; p.pad_l = pad_l;
-  const int CT = irb_pick_ct(C);
-  const int rows = irb_plan(p, N, Ho, Wo, C, stride, CT, stride == 2 ? 15 : 14, g_irb_waves > 0 ? g_irb_waves : 4096);
+  int CT = 0;
+  const int rows = dl3p_irb_fwd_plan_now(p, N, Ho, Wo, C, stride, &CT);
   if (rows_out) *rows_out = rows;
   hipStream_t st = (hipStream_t)stream;
   bool launched = false;
