@@ -1008,6 +1008,42 @@ int dl3p_mask_overlay_u8(const int* pred, const unsigned char* img, unsigned cha
                          const int* tables, const unsigned char* colormap, int n_valid, int alpha, int N, int H, int W, int h0, int w0,
                          void* stream);
 
+/* ---------------------------------------------------------------- hard-example mining (csrc/mining.hip)
+ * DeepLab's top_k_percent_pixels / hard_example_mining_step: the loss and its gradient come from the k pixels of the batch whose loss
+ * is highest.  Three stages in front of a weighted training head (dl3p_upsample_softmax_loss, dl3p_nearest_head_train), all fp32 with
+ * 64-bit offsets, integer counting only (workgroup-private LDS histograms flushed with integer atomics; no floating-point atomics),
+ * results bitwise repeatable.  P = N*H*W < 2^31.
+ * workspace: dl3p_mining_workspace() bytes on the device, 16-byte aligned, ZERO when the map is launched; a map launch followed by
+ * dl3p_topk_threshold leaves it zero again, so it is cleared once, when it is allocated.
+ * dl3p_pixel_loss_map / dl3p_nearest_pixel_loss_map: loss_map[N*H*W] = l_i, the per-pixel loss of dl3p_upsample_softmax_loss /
+ * dl3p_nearest_head_train before the inv_count mean: the loss kind's value (same clipping constants, class weights, focal parameters),
+ * times pixel_weights[i] (NULL: 1), and 0 where the head leaves the pixel out of its sum (label == ignore_index != 0, or outside
+ * [0, C)); -0.0 is stored as +0.0.  z, ldz, labels, (h, w) -> (H, W) as for those heads: bilinear with h <= H and w <= W (h == H:
+ * U-Net), nearest with H == r h, W == r w, 1 <= r <= 8.  No (N,H,W,C) tensor is written.  The same launch adds the first radix
+ * histogram of the map's keys (and the count of exact zeros) into the workspace.  DL3P_EINVAL before any launch: P >= 2^31, C outside
+ * [1, 256], ldz % 4 != 0 or ldz < C rounded up to 4, a base (z, loss_map, workspace) that is not 16-byte aligned, a null pointer, a bad
+ * loss kind, sizes the head does not serve.
+ * dl3p_topk_threshold: exact radix select over loss_map[P], 4 passes of 8 bits over the order-preserving key (sign bit flipped for
+ * l >= 0, all bits flipped for l < 0; -0.0 counts as +0.0, +inf lies above every finite value; where NaNs fall is unspecified), each
+ * pass a histogram launch and a one-workgroup scan; first_histogram_ready != 0: the map launch left the first histogram, else it is
+ * taken here (a map from elsewhere).  k = clamp(int(p P), 1, P) for M = mining_step == 0, else r = min(1, s / M) and
+ * k = clamp(int((r p + (1 - r)) P), 1, P), p = top_k_percent, in float64 in the order written, s = max(*step_counter + step_bias, 0)
+ * read on the device (step_counter NULL: s = 0).  record (8 words on the device, 16-byte aligned) = {int32 k, float theta, int32 m,
+ * int32 m_plus, float scale, 0, 0, 0}: theta the k-th largest l_i, m = |{l_i >= theta}| (every tie kept), m_plus of them != 0,
+ * scale = (float) (P / max(m_plus, 1)).  DL3P_EINVAL: P outside [1, 2^31), p outside (0, 1], M < 0, a misaligned or null pointer.
+ * dl3p_mining_weights: weights[i] = l_i >= theta ? base[i] * scale : 0 (base NULL: ones), 16-byte accesses; the pixel_weights of the
+ * head launch that follows, whose inv_count = 1 / P then turns sum(l_i w_i) into DeepLab's sum over the kept / max(m_plus, 1). */
+size_t dl3p_mining_workspace(void);
+int dl3p_pixel_loss_map(const float* z, int ldz, const float* labels, int ignore_index, int loss_kind, const float* class_weights,
+                        float focal_gamma, float focal_alpha, const float* pixel_weights, float* loss_map, void* workspace, int N,
+                        int h, int w, int C, int H, int W, void* stream);
+int dl3p_nearest_pixel_loss_map(const float* z, int ldz, const float* labels, int ignore_index, int loss_kind,
+                                const float* class_weights, float focal_gamma, float focal_alpha, const float* pixel_weights,
+                                float* loss_map, void* workspace, int N, int h, int w, int C, int H, int W, void* stream);
+int dl3p_topk_threshold(const float* loss_map, size_t P, double top_k_percent, int mining_step, const int64_t* step_counter,
+                        int step_bias, int first_histogram_ready, void* workspace, void* record, void* stream);
+int dl3p_mining_weights(const float* loss_map, const float* base, const void* record, float* weights, size_t P, void* stream);
+
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP
  * events (hipExtLaunchKernelGGL start/stop events on the launch stream) stored in slot i (0 <= i < 4096);

@@ -467,8 +467,12 @@ class BackwardTrace:
 class Executor:
     def __init__(self, graph, head, store, batch, training, num_classes, ignore_index=255, dist=None,
                  seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
-                 averaging=None, clip=None):
+                 averaging=None, clip=None, mining=None):
         self.g, self.head, self.store = graph, head, store
+        # hard-example mining: None | (top_k_percent_pixels, hard_example_mining_step) (losses.mining_spec): the loss and its gradient
+        # come from the k highest-loss pixels of this executor's batch (csrc/mining.hip)
+        self.mining = mining
+        self._mine_host, self._mine_evt, self._mine_posted = None, None, None
         self.opts = ExecOptions.from_env()      # every switch, fixed now for the life of this executor (exec_options.py)
         # gradient clipping: None | (clipvalue, clipnorm, global_clipnorm) (model clip_spec()), traced in front of the optimiser
         self.clip = clip if training else None
@@ -660,11 +664,19 @@ class Executor:
             self.class_weights = torch.from_numpy(self._loss_weights_host).to(self.dev)
         # Keras sample weights, sample_weight_mode='temporal' (train.py:116-120): ones until set_inputs receives some
         self.pixel_weights = torch.ones(N * H * W, **self.f32) if (self.training and self.sample_weighted) else None
+        # mining: the per-pixel loss map, the select's workspace (zero once: every select leaves it zero) and record, and the weights
+        # w_i = keep_i * (sample weight or 1) * P / max(m+, 1) the head reads -- a buffer of its own, the user's weights stay as set
+        self.loss_map = self.mining_ws = self.mining_record = self.mining_weights = None
+        if self.mining is not None and zt is not None:
+            self.loss_map = torch.zeros(N * H * W, **self.f32)
+            self.mining_weights = torch.zeros(N * H * W, **self.f32)
+            self.mining_ws = torch.zeros(L.mining_workspace() // 4, dtype=torch.int32, device=self.dev)
+            self.mining_record = torch.zeros(8, dtype=torch.int32, device=self.dev)
         # per-image class counts for the Jaccard training metric (deeplabv3p/metrics.py:29-46), refreshed every step
         self.metric_counts = (torch.zeros(N * 3 * self.C, dtype=torch.int32, device=self.dev).view(N, 3, self.C)
                               if (self.training and self.want_class_counts) else None)
         want = self.opts.fused_head       # the fused training heads, plain cross-entropy only: the `fused_head` row of exec_options.py
-        plain = bool(self.training and self.loss_kind == 0 and not self.sample_weighted and
+        plain = bool(self.training and self.loss_kind == 0 and not self.sample_weighted and self.mining is None and
                      self.class_weights is None and zt is not None and zt.requires_grad)
         # (the logits and their gradient stay fp32 under the bf16 policy -- _is_f32 -- so the separable head serves it too; the padded
         # classes of the gradient buffer are never written by anyone and keep the zeros they were allocated with)
@@ -1072,7 +1084,8 @@ class Executor:
         train = self.training
         if train:
             P.k(L.increment_counter, self.step.data_ptr())
-            if self.optimizer[0] == 'adam' or self.averaging is not None:      # (the averaging rules are gated by it too)
+            # (the averaging rules are gated by it too, and mining's ramp reads it)
+            if self.optimizer[0] == 'adam' or self.averaging is not None or self.mining is not None:
                 P.k(L.increment_counter, self.store.opt_step.data_ptr())
         self._fwd_pending, self._fwd_stage_off = [], 0
         self._irb_stage = {}
@@ -1165,17 +1178,36 @@ class Executor:
         self._head_forward(P)
         return P
 
+    def _mining_stages(self, launch, step_bias):
+        """map -> select -> weights in front of a weighted head launch (csrc/mining.hip); launch(fn, *args) issues one of them.
+        step_bias: the training plan has already counted the step it is in (-1), evaluate() reads the counter as it stands (0).
+        -> the device pointer of the weights the head takes as its pixel weights"""
+        L, zt, (p, M) = self.L, self.head.tensor, self.mining
+        base = None if self.pixel_weights is None else self.pixel_weights.data_ptr()
+        P = self.N * self.H * self.W
+        launch(L.nearest_pixel_loss_map if self.nearest_head else L.pixel_loss_map, self.tptr(zt), zt.ld, self.labels.data_ptr(),
+               int(self.ignore_index or 0), self.loss_kind, None if self.class_weights is None else self.class_weights.data_ptr(),
+               self.loss_gamma, self.loss_alpha, base, self.loss_map.data_ptr(), self.mining_ws.data_ptr(), self.N, zt.H, zt.W,
+               self.C, self.H, self.W)
+        launch(L.topk_threshold, self.loss_map.data_ptr(), P, p, M, self.store.opt_step.data_ptr(), step_bias, 1,
+               self.mining_ws.data_ptr(), self.mining_record.data_ptr())
+        launch(L.mining_weights, self.loss_map.data_ptr(), base, self.mining_record.data_ptr(), self.mining_weights.data_ptr(), P)
+        return self.mining_weights.data_ptr()
+
     def _head_forward(self, P):
         """pred_resize + softmax (+ loss and its gradient when training)"""
         L, N, train = self.L, self.N, self.training
         zt = self.head.tensor
         rows = ctypes.c_int(0)
+        pixel_w = None if self.pixel_weights is None else self.pixel_weights.data_ptr()
+        if train and self.mining is not None:
+            pixel_w = self._mining_stages(P.k, -1)
         if self.nearest_head:
             if train:
                 P.k(L.nearest_head_train, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
                     1.0 / float(N * self.H * self.W), self.loss_kind,
                     None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma, self.loss_alpha,
-                    None if self.pixel_weights is None else self.pixel_weights.data_ptr(),
+                    pixel_w,
                     self.tptr(zt, True) if zt.requires_grad else None, zt.ld, 0, self.loss_partials.data_ptr(), ctypes.byref(rows),
                     N, zt.H, zt.W, self.C, self.H, self.W)
                 P.k(L.reduce_rows, self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0)
@@ -1197,7 +1229,7 @@ class Executor:
             P.k(L.upsample_softmax_loss, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
                 1.0 / float(N * self.H * self.W), self.loss_kind,
                 None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma, self.loss_alpha,
-                None if self.pixel_weights is None else self.pixel_weights.data_ptr(),
+                pixel_w,
                 None, None, self.dlogits_big.data_ptr(), self.cpad,
                 self.loss_partials.data_ptr(), ctypes.byref(rows), N, zt.H, zt.W, self.C, self.H, self.W)
             P.k(L.reduce_rows, self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0)
@@ -2299,6 +2331,28 @@ class Executor:
             return float(np.sqrt(np.sum(h, dtype=np.float64)))
         return float(h[0])
 
+    def _post_mining(self):
+        """start the copy of this step's mining record {k, theta, m, m+, scale} to pinned host memory behind the plans (two slots, one
+        event each, like _post_grad_norm: the step never waits for the host)"""
+        if self._mine_host is None:
+            self._mine_host = [torch.zeros(8, dtype=torch.int32, pin_memory=True) for _ in range(2)]
+            self._mine_evt = [torch.cuda.Event(), torch.cuda.Event()]
+            self._mine_k = 0
+        i = self._mine_k & 1
+        self._mine_k += 1
+        self._mine_host[i].copy_(self.mining_record, non_blocking=True)
+        self._mine_evt[i].record()
+        self._mine_posted = i
+
+    def last_mining(self):
+        """{'k', 'threshold', 'kept', 'nonzero'} of the last train_step (None: no mining, or no step yet); waits for its copy only"""
+        i = self._mine_posted
+        if i is None:
+            return None
+        self._mine_evt[i].synchronize()
+        h = self._mine_host[i].numpy()
+        return {'k': int(h[0]), 'threshold': float(h[1:2].view(np.float32)[0]), 'kept': int(h[2]), 'nonzero': int(h[3])}
+
     # ---------------------------------------------------------------- running
     def _stage_u8(self, src, slot):
         src = torch.as_tensor(src).reshape(-1)
@@ -2401,6 +2455,8 @@ class Executor:
         self.opt.run()
         if self.clip is not None:
             self._post_grad_norm()
+        if self.mining is not None:
+            self._post_mining()
         if self.store.Sb is not None:
             self.store.sb_partial = self
 
@@ -2445,17 +2501,19 @@ class Executor:
         zt, L = self.head.tensor, self.L
         st = torch.cuda.current_stream().cuda_stream
         rows = ctypes.c_int(0)
+        # (mining: the validation loss is the mean over the kept set too, at the step count the optimiser stands at)
+        pixel_w = None if self.mining is None else self._mining_stages(lambda fn, *a: fn(*a, st), 0)
         if self.nearest_head:
             L.nearest_head_train(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
                                  1.0 / float(self.N * self.H * self.W), self.loss_kind,
                                  None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,
-                                 self.loss_alpha, None, None, 0, 0, self.loss_partials.data_ptr(), ctypes.byref(rows), self.N, zt.H,
+                                 self.loss_alpha, pixel_w, None, 0, 0, self.loss_partials.data_ptr(), ctypes.byref(rows), self.N, zt.H,
                                  zt.W, self.C, self.H, self.W, st)
         else:
             L.upsample_softmax_loss(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
                                     1.0 / float(self.N * self.H * self.W), self.loss_kind,
                                     None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,
-                                    self.loss_alpha, None, None, None, None, self.cpad, self.loss_partials.data_ptr(),
+                                    self.loss_alpha, pixel_w, None, None, None, self.cpad, self.loss_partials.data_ptr(),
                                     ctypes.byref(rows), self.N, zt.H, zt.W, self.C, self.H, self.W, st)
         L.reduce_rows(self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0, st)
         if counts is not None:

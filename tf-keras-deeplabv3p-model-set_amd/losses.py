@@ -3,12 +3,24 @@ the host arithmetic on what the device counts: jaccard_from_counts, miou_from_co
 import numpy as np
 
 
+def _check_mining(top_k_percent_pixels, hard_example_mining_step):
+    """the hard-example mining keywords every loss takes (DeepLab's train_utils.add_softmax_cross_entropy_loss_for_each_scale):
+    0 < top_k_percent_pixels <= 1 (1.0: off), hard_example_mining_step an integer >= 0 (0: no ramp) -> (p, M)"""
+    p, M = top_k_percent_pixels, hard_example_mining_step
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 < float(p) <= 1.0:
+        raise ValueError('top_k_percent_pixels must lie in (0, 1], got %r' % (p,))
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or int(M) < 0:
+        raise ValueError('hard_example_mining_step must be an integer >= 0, got %r' % (M,))
+    return float(p), int(M)
+
+
 class SparseCategoricalCrossEntropy(object):
     """deeplabv3p/loss.py:121-156: configuration holder -- the arithmetic is fused into the HIP head kernel"""
 
-    def __init__(self, ignore_index=None, from_logits=False):
+    def __init__(self, ignore_index=None, from_logits=False, *, top_k_percent_pixels=1.0, hard_example_mining_step=0):
         if from_logits:
             raise ValueError('the model emits probabilities (Softmax pred_mask); from_logits is not supported')
+        self.top_k_percent_pixels, self.hard_example_mining_step = _check_mining(top_k_percent_pixels, hard_example_mining_step)
         self.ignore_index = ignore_index
         self.from_logits = from_logits
         self.__name__ = 'sparse_categorical_crossentropy'
@@ -17,9 +29,10 @@ class SparseCategoricalCrossEntropy(object):
 class WeightedSparseCategoricalCrossEntropy(object):
     """deeplabv3p/loss.py:159-191 (train.py:115, --weighted_type balanced): -w[y] * log(p_y)"""
 
-    def __init__(self, weights, ignore_index=None, from_logits=False):
+    def __init__(self, weights, ignore_index=None, from_logits=False, *, top_k_percent_pixels=1.0, hard_example_mining_step=0):
         if from_logits:
             raise ValueError('the model emits probabilities (Softmax pred_mask); from_logits is not supported')
+        self.top_k_percent_pixels, self.hard_example_mining_step = _check_mining(top_k_percent_pixels, hard_example_mining_step)
         self.weights = np.array(weights).astype('float32')
         self.ignore_index = ignore_index
         self.from_logits = from_logits
@@ -29,9 +42,11 @@ class WeightedSparseCategoricalCrossEntropy(object):
 class SparseSoftmaxFocalLoss(object):
     """deeplabv3p/loss.py:63-118 (train.py:131, --loss focal): -alpha * (1 - p_y)^gamma * log(p_y)"""
 
-    def __init__(self, gamma=2.0, alpha=0.25, ignore_index=None, from_logits=False):
+    def __init__(self, gamma=2.0, alpha=0.25, ignore_index=None, from_logits=False, *, top_k_percent_pixels=1.0,
+                 hard_example_mining_step=0):
         if from_logits:
             raise ValueError('the model emits probabilities (Softmax pred_mask); from_logits is not supported')
+        self.top_k_percent_pixels, self.hard_example_mining_step = _check_mining(top_k_percent_pixels, hard_example_mining_step)
         self.gamma, self.alpha = gamma, alpha
         self.ignore_index = ignore_index
         self.from_logits = from_logits
@@ -74,6 +89,15 @@ def loss_spec(loss):
     if isinstance(loss, SparseSoftmaxFocalLoss):
         return ('focal', float(loss.gamma), float(loss.alpha))
     return ('ce',)
+
+
+def mining_spec(loss):
+    """-> None (every pixel trains: top_k_percent_pixels == 1.0) | (p, M): the loss and its gradient come from the
+    k = int((r p + 1 - r) P) highest-loss pixels of the batch, r = min(1, step / M) (csrc/mining.hip)"""
+    p = float(getattr(loss, 'top_k_percent_pixels', 1.0))
+    if p == 1.0:
+        return None
+    return (p, int(getattr(loss, 'hard_example_mining_step', 0)))
 
 
 def miou_from_confusion(cm, class_names=None):

@@ -18,7 +18,7 @@ from .mobilenetv2 import Deeplabv3pMobileNetV2, Deeplabv3pLiteMobileNetV2
 from .optimizers import (_clip_args, SGD, Adam, RMSprop, _AveragedOptimizer, MovingAverage, SWA, Lookahead,  # noqa: F401
                          get_averaged_optimizer, get_optimizer)
 from .losses import (SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy, SparseSoftmaxFocalLoss, Jaccard,  # noqa: F401
-                     jaccard_from_counts, _wants_jaccard, loss_spec, miou_from_confusion)
+                     jaccard_from_counts, _wants_jaccard, loss_spec, mining_spec, miou_from_confusion)
 from .feed import DistContext, StagedBatch, BatchFeeder, LateScalar  # noqa: F401
 from .callbacks import EvalCallBack, AverageModelCheckpoint  # noqa: F401
 
@@ -281,6 +281,15 @@ class DeeplabModel:
         ex = self._last_train_ex
         return ex.last_grad_norm() if ex is not None else None
 
+    @property
+    def last_mining(self):
+        """what hard-example mining selected in the last training step: {'k': size of the kept set the rule asked for, 'threshold':
+        the k-th largest per-pixel loss, 'kept': pixels at or above it (ties included), 'nonzero': of those, the ones whose loss is
+        not 0 (the loss' normaliser)}; None without mining (top_k_percent_pixels == 1.0) or before the first step.  Like
+        last_grad_norm the record follows its step to the host asynchronously: reading it waits for that copy only."""
+        ex = self._last_train_ex
+        return ex.last_mining() if ex is not None else None
+
     def _executor(self, batch, training):
         avg = self._avg_spec() if training else None
         clip = self._clip_spec() if training else None
@@ -297,7 +306,7 @@ class DeeplabModel:
                                        ignore_index=ignore, dist=self.dist if training else None,
                                        seed=self.seed + 7919 * rank, loss=loss_spec(self.loss), optimizer=opt,
                                        sample_weighted=self.sample_weight_mode == 'temporal',
-                                       class_counts=self._jaccard, averaging=avg, clip=clip)
+                                       class_counts=self._jaccard, averaging=avg, clip=clip, mining=mining_spec(self.loss))
         return self._exec[key]
 
     def train_on_batch(self, x, y, sample_weight=None, return_tensor=False):

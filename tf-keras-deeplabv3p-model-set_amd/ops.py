@@ -1438,3 +1438,51 @@ def nearest_class_counts(z, C, H, W, labels):
     counts = torch.zeros((N, 3, C), dtype=torch.int32, device=z.device)
     lib().nearest_class_counts(zp, ldz, _p(labels), _p(counts), N, h, w, C, H, W, _stream())
     return counts
+
+
+# ---------------------------------------------------------------- hard-example mining (csrc/mining.hip)
+def mining_workspace(device):
+    """the select's workspace: zero once, every pixel_loss_map + topk_threshold pair leaves it zero again"""
+    return torch.zeros(lib().mining_workspace() // 4, dtype=torch.int32, device=device)
+
+
+def pixel_loss_map(z, C, H, W, labels, ignore_index=255, loss=('ce',), pixel_weights=None, nearest=False, out=None, workspace=None):
+    """z (N,h,w,Cpad) logits, labels [N*H*W] -> (per-pixel loss map [N*H*W] as the weighted head defines it, before the mean; the
+    workspace, now holding the first radix histogram of the map).  nearest: the head behind UpSampling2D (dl3p_nearest_head_train),
+    else the bilinear one (dl3p_upsample_softmax_loss); loss as upsample_softmax_ce"""
+    N, h, w, _ = z.shape
+    zp, ldz = _pl(z)
+    if out is None:
+        out = torch.empty(N * H * W, dtype=torch.float32, device=z.device)
+    if workspace is None:
+        workspace = mining_workspace(z.device)
+    kind = {'ce': 0, 'weighted': 1, 'focal': 2}[loss[0]]
+    cw = loss[1] if kind == 1 else None
+    gamma, alpha = (float(loss[1]), float(loss[2])) if kind == 2 else (0.0, 0.0)
+    fn = lib().nearest_pixel_loss_map if nearest else lib().pixel_loss_map
+    fn(zp, ldz, _p(labels), int(ignore_index or 0), kind, _p(cw), gamma, alpha, _p(pixel_weights), _p(out), _p(workspace), N, h, w,
+       C, H, W, _stream())
+    return out, workspace
+
+
+def topk_threshold(loss_map, top_k_percent_pixels, hard_example_mining_step=0, step_counter=None, step_bias=0, workspace=None,
+                   record=None):
+    """exact k-th largest of loss_map [P] -> record, int32 [8] on the device: {k, threshold bits, kept, nonzero, scale bits, 0, 0, 0}.
+    workspace: the one pixel_loss_map returned (its first histogram is used), or None for a map from elsewhere;
+    step_counter: int64 [1] on the device (None: step 0)"""
+    first_ready = workspace is not None
+    if workspace is None:
+        workspace = mining_workspace(loss_map.device)
+    if record is None:
+        record = torch.zeros(8, dtype=torch.int32, device=loss_map.device)
+    lib().topk_threshold(_p(loss_map), loss_map.numel(), float(top_k_percent_pixels), int(hard_example_mining_step),
+                         _p(step_counter), int(step_bias), int(first_ready), _p(workspace), _p(record), _stream())
+    return record
+
+
+def mining_weights(loss_map, record, base=None, out=None):
+    """-> w [P] = (loss_map >= threshold) ? base * scale : 0 (base None: ones): the pixel weights of the head launch that follows"""
+    if out is None:
+        out = torch.empty_like(loss_map)
+    lib().mining_weights(_p(loss_map), _p(base), _p(record), _p(out), loss_map.numel(), _stream())
+    return out
