@@ -255,6 +255,64 @@ def test_nearest_loss_map(ops, r, C):
     assert _check_maps(ops, True, 2, 2, 3, C, 2 * r, 3 * r)
 
 
+def _check_map_is_the_heads_loss(ops, nearest, N, h, w, C, H, W):
+    """map[i] == the head's reduced loss under pixel weights that are 1.0 at pixel i and 0 elsewhere, with inv_count = 1: every
+    other term of the head's sums is an exact zero, so the two share all 32 bits where they share the per-pixel expression"""
+    P = N * H * W
+    z, y, _, cw = _head_case(N, h, w, C, H, W, 7 * C + h, True, False)
+    y = y.reshape(-1)
+    ignored_px = 1
+    pixels = [0, P - 1, H * W, H * W + W - 1, P - W, P - 1, (H // 2) * W + W // 2]     # first, last, image 1's corners, interior
+    assert ignored_px not in pixels
+    rng = np.random.default_rng(3)
+    for i in pixels:
+        if y[i] == 255:
+            y[i] = rng.integers(0, C)
+    y[ignored_px] = 255
+    dz, dy = torch.from_numpy(z).to(DEV), torch.from_numpy(y).to(DEV)
+    full = R.nearest_logits(z[..., :C], H // h) if nearest else R.bilinear_logits(z[..., :C], H, W)
+    st = torch.cuda.current_stream().cuda_stream
+    partial = torch.zeros(ops.MAX_STAT_ROWS, dtype=torch.float32, device=DEV)
+    total = torch.empty(1, dtype=torch.float32, device=DEV)
+    for kind, spec, dspec, args in ((0, ('ce',), ('ce',), (None, 0.0, 0.0)),
+                                    (1, ('weighted', cw), ('weighted', torch.from_numpy(cw).to(DEV)), None),
+                                    (2, ('focal', 2.0, 0.25), ('focal', 2.0, 0.25), (None, 2.0, 0.25))):
+        if args is None:
+            args = (dspec[1].data_ptr(), 0.0, 0.0)
+        want = R.pixel_losses(full, y.reshape(N, H, W), spec, 255, None)
+        assert all(np.isfinite(want[i]) and want[i] > 0 for i in pixels), (spec[0], [want[i] for i in pixels])
+        lmap = ops.pixel_loss_map(dz, C, H, W, dy, 255, dspec, None, nearest=nearest)[0].cpu().numpy()
+        for i in pixels + [ignored_px]:
+            onehot = torch.zeros(P, dtype=torch.float32, device=DEV)
+            onehot[i] = 1.0
+            rows = ctypes.c_int(0)
+            if nearest:
+                ops.lib().nearest_head_train(dz.data_ptr(), dz.shape[-1], dy.data_ptr(), 255, 1.0, kind, *args, onehot.data_ptr(), None,
+                                             0, 0, partial.data_ptr(), ctypes.byref(rows), N, h, w, C, H, W, st)
+            else:
+                ops.lib().upsample_softmax_loss(dz.data_ptr(), dz.shape[-1], dy.data_ptr(), 255, 1.0, kind, *args, onehot.data_ptr(),
+                                                None, None, None, dz.shape[-1], partial.data_ptr(), ctypes.byref(rows), N, h, w, C,
+                                                H, W, st)
+            ops.lib().reduce_rows(partial.data_ptr(), rows.value, 1, total.data_ptr(), 0, st)
+            head = total.cpu().numpy()
+            print('%s C %d %s pixel %d: head %.9g map %.9g' % ('nearest' if nearest else 'bilinear', C, spec[0], i, head[0], lmap[i]))
+            assert _bits(head)[0] == _bits(lmap[i:i + 1])[0], (spec[0], i, float(head[0]), float(lmap[i]))
+            if i == ignored_px:
+                assert _bits(head)[0] == 0 and _bits(lmap[i:i + 1])[0] == 0
+    return True
+
+
+@pytest.mark.parametrize('C', [2, 21, 40])
+def test_bilinear_loss_map_is_the_heads_loss_bit_for_bit(ops, C):
+    assert _check_map_is_the_heads_loss(ops, False, 2, 3, 4, C, 5, 7)
+
+
+@pytest.mark.parametrize('C', [2, 21, 40])
+@pytest.mark.parametrize('r', [1, 8])
+def test_nearest_loss_map_is_the_heads_loss_bit_for_bit(ops, r, C):
+    assert _check_map_is_the_heads_loss(ops, True, 2, 2, 3, C, 2 * r, 3 * r)
+
+
 def test_the_weighted_head_reports_the_rules_loss(ops):
     """map -> select -> weights -> dl3p_upsample_softmax_loss / dl3p_nearest_head_train: the head's sum of l_i w_i / P is the rule's
     sum over the kept / max(m+, 1), which holds by construction (w_i carries P / m+)"""

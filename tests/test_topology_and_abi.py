@@ -167,6 +167,15 @@ def test_c_abi_exports_every_declared_symbol():
                        4, 4, None)
 
 
+def test_the_head_kernels_share_one_bilinear_rule_and_one_loss_term():
+    """the half-pixel source coordinate and the focal term are written once (csrc/head_common.h): the kernels that promise each
+    other's bits call them, they do not restate them"""
+    csrc = os.path.join(ROOT, 'tf-keras-deeplabv3p-model-set_amd', 'csrc')
+    for text in ('+ 0.5f) * scale - 0.5f', 'powf(om,'):
+        files = sorted(f for f in os.listdir(csrc) if text in open(os.path.join(csrc, f), errors='replace').read())
+        assert files == ['head_common.h'], (text, files)
+
+
 def test_dispatch_options_and_tile_table():
     """dl3p_set_option: the knobs the tile tuner (scripts/tune_gemm.py) and the small-shape tests move; the measured tile
     table is well-formed (host-side only, no GPU)"""

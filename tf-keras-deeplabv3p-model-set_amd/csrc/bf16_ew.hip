@@ -4,6 +4,7 @@
 // bn_elementwise.hip / resize_head.hip / conv.hip; tensors in HBM are bf16, all arithmetic is fp32 (bf16.h states the
 // rounding points).  HBM-bound: 16-byte lanes (8 channels) when C % 8 == 0, 8-byte lanes otherwise; channel lanes fastest.
 #include "bf16.h"
+#include "head_common.h"
 
 namespace {
 
@@ -474,16 +475,6 @@ extern "C" int dl3p_scale_bcast_bwd_bf16(const void* gy, int ldgy, const void* x
 
 // ------------------------------------------------------------------------------ bilinear resize
 namespace {
-struct LerpB { int lo, hi; float t; };
-__device__ __forceinline__ LerpB lerp_b(int o, float scale, int in_size) {
-  const float src = ((float)o + 0.5f) * scale - 0.5f;
-  const float fl = floorf(src);
-  LerpB r;
-  r.lo = max((int)fl, 0);
-  r.hi = min((int)ceilf(src), in_size - 1);
-  r.t = src - fl;
-  return r;
-}
 struct ResizeB {
   const bf16* x; int ldx; bf16* y; int ldy;
   int N, h, w, C, H, W, cs, px, nslab, nbx;
@@ -505,17 +496,13 @@ __global__ __launch_bounds__(256) void resize_fwd_b(ResizeB p) {
   for (int s = bx * p.px + pl; s < total; s += step) {
     const int row = s / p.W, ox = s - row * p.W;
     const int n = row / p.H, oy = row - n * p.H;
-    const LerpB ly = lerp_b(oy, sy, p.h), lx = lerp_b(ox, sx, p.w);
+    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
     const bf16* img = p.x + (size_t)n * p.h * p.w * p.ldx + c;
     const fvec<V> tl = ldv<V>(img + ((size_t)ly.lo * p.w + lx.lo) * p.ldx), tr = ldv<V>(img + ((size_t)ly.lo * p.w + lx.hi) * p.ldx);
     const fvec<V> bl = ldv<V>(img + ((size_t)ly.hi * p.w + lx.lo) * p.ldx), br = ldv<V>(img + ((size_t)ly.hi * p.w + lx.hi) * p.ldx);
     fvec<V> o;
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const float top = tl.v[i] + (tr.v[i] - tl.v[i]) * lx.t;
-      const float bot = bl.v[i] + (br.v[i] - bl.v[i]) * lx.t;
-      o.v[i] = top + (bot - top) * ly.t;
-    }
+    for (int i = 0; i < V; ++i) o.v[i] = lerp2(tl.v[i], tr.v[i], bl.v[i], br.v[i], lx.t, ly.t);
     stv<V>(p.y + (size_t)s * p.ldy + c, o);
   }
 }
@@ -550,11 +537,11 @@ __global__ __launch_bounds__(256) void resize_bwd_b(ResizeB p) {
     fvec<V> acc = fzero<V>();
     const bf16* gimg = p.x + (size_t)n * p.H * p.W * p.ldx + c;
     for (int oy = y0; oy <= y1; ++oy) {
-      const LerpB ly = lerp_b(oy, sy, p.h);
+      const Lerp ly = lerp_coeff(oy, sy, p.h);
       const float wy = (ly.lo == iy ? 1.f - ly.t : 0.f) + (ly.hi == iy ? ly.t : 0.f);
       if (wy == 0.f) continue;
       for (int ox = x0; ox <= x1; ++ox) {
-        const LerpB lx = lerp_b(ox, sx, p.w);
+        const Lerp lx = lerp_coeff(ox, sx, p.w);
         const float wx = (lx.lo == ix ? 1.f - lx.t : 0.f) + (lx.hi == ix ? lx.t : 0.f);
         if (wx == 0.f) continue;
         const float wgt = wy * wx;

@@ -13,6 +13,7 @@
 // The BN+activation of the producing layer is applied on load (prologue): zero padding is in
 // activation space, so out-of-range taps contribute exactly 0.
 #include "bf16.h"
+#include "head_common.h"
 #include "options.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -51,29 +52,13 @@ struct DwParams {
   const float* up_x; int up_ld, up_h, up_w, up_C;
 };
 
-// dl3p_resize_bilinear_fwd's source coordinates (csrc/resize_head.hip lerp_coeff: TF2 half-pixel centres), restated here
-struct DwLerp { int lo, hi; float t; };
-__device__ __forceinline__ DwLerp dw_lerp(int o, float scale, int in_size) {
-  const float src = ((float)o + 0.5f) * scale - 0.5f;
-  const float fl = floorf(src);
-  DwLerp r;
-  r.lo = max((int)fl, 0);
-  r.hi = min((int)ceilf(src), in_size - 1);
-  r.t = src - fl;
-  return r;
-}
-// one input vector of an UP launch: the four neighbours of (iy, ix) in the low-resolution map, TF's order of operations
-// (top = tl + (tr - tl) tx; bottom = bl + (br - bl) tx; out = top + (bottom - top) ty)
-__device__ __forceinline__ float4 dw_up_load(const float* img, int up_w, int up_ld, DwLerp ly, DwLerp lx) {
+// one input vector of an UP launch: the four neighbours of (iy, ix) in the low-resolution map
+__device__ __forceinline__ float4 dw_up_load(const float* img, int up_w, int up_ld, Lerp ly, Lerp lx) {
   const float4 tl = ld4(img + ((size_t)ly.lo * up_w + lx.lo) * up_ld);
   const float4 tr = ld4(img + ((size_t)ly.lo * up_w + lx.hi) * up_ld);
   const float4 bl = ld4(img + ((size_t)ly.hi * up_w + lx.lo) * up_ld);
   const float4 br = ld4(img + ((size_t)ly.hi * up_w + lx.hi) * up_ld);
-  float4 o;
-#define DW_LERP2(f) { const float top = tl.f + (tr.f - tl.f) * lx.t; const float bot = bl.f + (br.f - bl.f) * lx.t; o.f = top + (bot - top) * ly.t; }
-  DW_LERP2(x) DW_LERP2(y) DW_LERP2(z) DW_LERP2(w)
-#undef DW_LERP2
-  return o;
+  return lerp2(tl, tr, bl, br, lx.t, ly.t);
 }
 
 // g' = g * act'(z*scale+shift), xhat = (z - mean) * invstd  ->  s[0] += g', s[1] += g' * xhat
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(256, (KS == 5 && S == 2 && PRO == 2 && !FAST_K) ? 2
         coff[i] = ix * p.ldx;
       }
       // UP: the column coefficients of the strip's input pixels in the low-resolution map (rows: per input row below)
-      DwLerp lxs[UP ? SEG : 1];
+      Lerp lxs[UP ? SEG : 1];
       const bool upl = UP && c < p.up_C;
       const float* uimg = nullptr;
       float usy = 0.f;
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(256, (KS == 5 && S == 2 && PRO == 2 && !FAST_K) ? 2
         const float usx = (float)p.up_w / (float)p.W;
         usy = (float)p.up_h / (float)p.H;
 #pragma unroll
-        for (int i = 0; i < SEG; ++i) lxs[i] = dw_lerp(min(max(ix0 + i * rate, 0), p.W - 1), usx, p.up_w);
+        for (int i = 0; i < SEG; ++i) lxs[i] = lerp_coeff(min(max(ix0 + i * rate, 0), p.W - 1), usx, p.up_w);
         uimg = p.up_x + (size_t)n * p.up_h * p.up_w * p.up_ld + (upl ? c : 0);
       }
       float4 win[KS][SEG];
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(256, (KS == 5 && S == 2 && PRO == 2 && !FAST_K) ? 2
 #pragma unroll
           for (int i = 0; i < SEG; ++i) {
             win[ky][i] = zero4();
-            if (yok && cok[i]) win[ky][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
+            if (yok && cok[i]) win[ky][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, lerp_coeff(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
           }
         }
 #pragma unroll
@@ -311,7 +296,7 @@ __global__ __launch_bounds__(256, (KS == 5 && S == 2 && PRO == 2 && !FAST_K) ? 2
 #pragma unroll
           for (int i = 0; i < SEG; ++i) {
             raw[q][i] = zero4();
-            if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
+            if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, lerp_coeff(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
           }
         }
         float4 acc[TW];
@@ -706,7 +691,7 @@ __global__ __launch_bounds__(256, (BNA && !UP) ? 2 : 1) void dw_bwd_weight_seg(D
         coff[i] = ix * p.ldx;
       }
       // UP: the column coefficients of the strip's input pixels in the low-resolution map (rows: per input row below)
-      DwLerp lxs[UP ? SEG : 1];
+      Lerp lxs[UP ? SEG : 1];
       const bool upl = UP && c < p.up_C;
       const float* uimg = nullptr;
       float usy = 0.f;
@@ -714,7 +699,7 @@ __global__ __launch_bounds__(256, (BNA && !UP) ? 2 : 1) void dw_bwd_weight_seg(D
         const float usx = (float)p.up_w / (float)p.W;
         usy = (float)p.up_h / (float)p.H;
 #pragma unroll
-        for (int i = 0; i < SEG; ++i) lxs[i] = dw_lerp(min(max(ix0 + i * rate, 0), p.W - 1), usx, p.up_w);
+        for (int i = 0; i < SEG; ++i) lxs[i] = lerp_coeff(min(max(ix0 + i * rate, 0), p.W - 1), usx, p.up_w);
         uimg = p.up_x + (size_t)n * p.up_h * p.up_w * p.up_ld + (upl ? c : 0);
       }
       float4 win[KS][SEG];
@@ -730,7 +715,7 @@ __global__ __launch_bounds__(256, (BNA && !UP) ? 2 : 1) void dw_bwd_weight_seg(D
 #pragma unroll
           for (int i = 0; i < SEG; ++i) {
             win[ky][i] = zero4();
-            if (yok && cok[i]) win[ky][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
+            if (yok && cok[i]) win[ky][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, lerp_coeff(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
           }
         }
 #pragma unroll
@@ -758,7 +743,7 @@ __global__ __launch_bounds__(256, (BNA && !UP) ? 2 : 1) void dw_bwd_weight_seg(D
 #pragma unroll
           for (int i = 0; i < SEG; ++i) {
             raw[q][i] = zero4();
-            if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, dw_lerp(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
+            if (nyok[q] && cok[i]) raw[q][i] = (UP && upl) ? dw_up_load(uimg, p.up_w, p.up_ld, lerp_coeff(iy, usy, p.up_h), lxs[UP ? i : 0]) : ld4(xrow + coff[i]);
           }
         }
         // gradient of the raw conv output for this row's strip

@@ -5,9 +5,9 @@
 //            histogram launch and a one-workgroup scan that narrows the prefix and the remaining rank
 //   weights  w_i = (l_i >= theta) * base_i * scale, the pixel_weights buffer the head reads next
 // Counting is done in integers only (workgroup-private LDS bins flushed with integer atomics, like argmax_confusion_kernel), so
-// every result is the same bit for bit in any order.  Per-pixel loss definitions, clipping constants and masking are those of
-// head_kernel (csrc/resize_head.hip) and nearest_head_train_kernel (csrc/nearest_head.hip).
-#include "common.h"
+// every result is the same bit for bit in any order.  Per-pixel loss definitions, clipping constants and masking are the training
+// heads': loss_term and label_valid of csrc/head_common.h.
+#include "head_common.h"
 
 namespace {
 
@@ -68,34 +68,13 @@ struct MapParams {
   long long total;
 };
 
-// l(p_t) of head_kernel, times the pixel weight, 0 for a pixel the head leaves out of its sum; -0.0 becomes +0.0
+// loss_term's l(p_t) times the pixel weight, 0 for a pixel the head leaves out of its sum; -0.0 becomes +0.0
 __device__ __forceinline__ float pixel_loss(const MapParams& p, float pt, bool valid, int lab, float sw) {
-  float li;
-  if (p.loss_kind == DL3P_LOSS_WEIGHTED_CE) {
-    const float wy = valid ? p.class_w[lab] : 0.f;
-    li = -wy * logf(pt);
-  } else if (p.loss_kind == DL3P_LOSS_FOCAL) {
-    const float pc = fmaxf(pt, 1e-15f);
-    const float om = 1.f - pc, lp = logf(pc);
-    const float pw1 = om > 0.f ? powf(om, p.focal_gamma - 1.f) : (p.focal_gamma == 1.f ? 1.f : 0.f);
-    li = -p.focal_alpha * (pw1 * om) * lp;
-  } else {
-    li = -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-  }
+  float li, f;
+  loss_term(p.loss_kind, pt, valid, lab, p.class_w, p.focal_gamma, p.focal_alpha, &li, &f);
   li *= sw;
   if (!valid || li == 0.f) li = 0.f;
   return li;
-}
-
-struct Lerp { int lo, hi; float t; };
-__device__ __forceinline__ Lerp lerp_coeff(int o, float scale, int in_size) {      // the rule of dl3p_resize_bilinear_fwd
-  const float src = ((float)o + 0.5f) * scale - 0.5f;
-  const float fl = floorf(src);
-  Lerp r;
-  r.lo = max((int)fl, 0);
-  r.hi = min((int)ceilf(src), in_size - 1);
-  r.t = src - fl;
-  return r;
 }
 
 // one thread per full-resolution pixel; CP > 0: the padded class vector in registers (head_kernel), CP == 0: three walks over the
@@ -104,52 +83,23 @@ template <int CP>
 __global__ __launch_bounds__(256) void loss_map_kernel(MapParams p) {
   __shared__ unsigned lds[257];
   const Bins b = bins_begin(lds, p.ws, 0);
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
   for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
-    const int ox = (int)(s % p.W);
-    const long long row = s / p.W;
-    const int oy = (int)(row % p.H);
-    const long long n = row / p.H;
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
+    int ox, oy;
+    long long n;
+    pixel_of(s, p.W, p.H, &ox, &oy, &n);
+    const Taps t(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W);
     const int lab = (int)p.labels[s];
-    const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-    const bool valid = !masked && lab >= 0 && lab < p.C;
+    const bool valid = label_valid(lab, p.ignore_index, p.C);
     float pt = 0.f;
     if constexpr (CP > 0) {
       float v[CP];
+      tap_logits<CP>(v, t);
+      const float inv = softmax_exp<CP>(v, p.C);
 #pragma unroll
-      for (int c4 = 0; c4 < CP / 4; ++c4) {
-        const float4 tl = ld4(ptl + c4 * 4), tr = ld4(ptr + c4 * 4), bl = ld4(pbl + c4 * 4), br = ld4(pbr + c4 * 4);
-#define LERP2(f, i) { float top = tl.f + (tr.f - tl.f) * lx.t; float bot = bl.f + (br.f - bl.f) * lx.t; v[c4 * 4 + i] = top + (bot - top) * ly.t; }
-        LERP2(x, 0) LERP2(y, 1) LERP2(z, 2) LERP2(w, 3)
-#undef LERP2
-      }
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) if (c < p.C) mx = fmaxf(mx, v[c]);
-      float sum = 0.f, et = 0.f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) {
-        const float e = c < p.C ? __expf(v[c] - mx) : 0.f;
-        sum += e;
-        if (c == lab) et = e;
-      }
-      pt = et * (1.f / sum);
+      for (int c = 0; c < CP; ++c) if (c == lab) pt = v[c] * inv;
     } else {
-      auto logit = [&](int c) {
-        const float top = ptl[c] + (ptr[c] - ptl[c]) * lx.t, bot = pbl[c] + (pbr[c] - pbl[c]) * lx.t;
-        return top + (bot - top) * ly.t;
-      };
-      float mx = -3.0e38f;
-      for (int c = 0; c < p.C; ++c) mx = fmaxf(mx, logit(c));
-      float sum = 0.f;
-      for (int c = 0; c < p.C; ++c) sum += __expf(logit(c) - mx);
-      pt = valid ? __expf(logit(lab) - mx) * (1.f / sum) : 0.f;
+      const SoftmaxWalk k = softmax_walk(t, p.C);
+      pt = valid ? k.prob(lab) : 0.f;
     }
     const float l = pixel_loss(p, pt, valid, lab, p.pixel_w ? p.pixel_w[s] : 1.f);
     p.map[s] = l;
@@ -159,40 +109,17 @@ __global__ __launch_bounds__(256) void loss_map_kernel(MapParams p) {
 }
 
 // behind a nearest upsampling: a wave owns a logit pixel, lane l holds the classes [4 l, 4 l + 4) and the label l of the r x r block
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void nearest_loss_map_kernel(MapParams p) {
   __shared__ unsigned lds[257];
   const Bins b = bins_begin(lds, p.ws, 0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int rr = p.r * p.r;
   const int li = lane / p.r, lj = lane - li * p.r;
-  const int c0 = lane * 4;
   for (long long s = (long long)blockIdx.x * 4 + wave; s < p.total; s += (long long)gridDim.x * 4) {   // wave-uniform
-    const int x = (int)(s % p.w);
-    const long long t = s / p.w;
-    const int y = (int)(t % p.h);
-    const long long n = t / p.h;
-    // the softmax of nearest_head.hip's wave_softmax, op for op
-    const float* zp = p.z + (size_t)s * p.ldz;
-    float4 v = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
-    if (c0 < p.cp) v = ld4(zp + c0);
-    const bool i0 = c0 < p.C, i1 = c0 + 1 < p.C, i2 = c0 + 2 < p.C, i3 = c0 + 3 < p.C;
-    float mx = fmaxf(fmaxf(i0 ? v.x : -3.0e38f, i1 ? v.y : -3.0e38f), fmaxf(i2 ? v.z : -3.0e38f, i3 ? v.w : -3.0e38f));
-    mx = wave_max(mx);
-    const float4 e = make_float4(i0 ? __expf(v.x - mx) : 0.f, i1 ? __expf(v.y - mx) : 0.f, i2 ? __expf(v.z - mx) : 0.f,
-                                 i3 ? __expf(v.w - mx) : 0.f);
-    const float inv = 1.f / wave_sum((e.x + e.y) + (e.z + e.w));
-    const float4 pr = make_float4(e.x * inv, e.y * inv, e.z * inv, e.w * inv);
+    int x, y;
+    long long n;
+    pixel_of(s, p.w, p.h, &x, &y, &n);
+    const float4 pr = wave_softmax(p.z + (size_t)s * p.ldz, lane, p.C, p.cp);
     int lab = -1;
     float swt = 1.f;
     size_t f = 0;
@@ -201,13 +128,9 @@ __global__ __launch_bounds__(256) void nearest_loss_map_kernel(MapParams p) {
       lab = (int)p.labels[f];
       if (p.pixel_w) swt = p.pixel_w[f];
     }
-    const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-    const bool valid = lane < rr && !masked && lab >= 0 && lab < p.C;
+    const bool valid = lane < rr && label_valid(lab, p.ignore_index, p.C);
     if (!valid) lab = -1;
-    const int src = valid ? (lab >> 2) : 0;
-    const float q0 = __shfl(pr.x, src), q1 = __shfl(pr.y, src), q2 = __shfl(pr.z, src), q3 = __shfl(pr.w, src);
-    const int comp = lab & 3;
-    const float pt = valid ? (comp == 0 ? q0 : comp == 1 ? q1 : comp == 2 ? q2 : q3) : 1.f;
+    const float pt = wave_label_prob(pr, valid, lab);
     const float l = pixel_loss(p, pt, valid, valid ? lab : 0, swt);
     if (lane < rr) {
       p.map[f] = l;

@@ -1,9 +1,9 @@
 // The head behind a nearest UpSampling2D((r, r)) (fast_scnn/models/fast_scnn.py:143-149): the r x r pixels of a block share ONE logit
 // vector, so one softmax per logit pixel serves the whole block and the gradient of that vector is the sum over the block's labels.
 // A wave owns a logit pixel: lane l holds the classes [4 l, 4 l + 4) (256 classes at most) and, in the training kernel, the label
-// k = l of the block (r * r <= 64).  Per-pixel loss definitions, clipping constants and masking are those of head_kernel
-// (csrc/resize_head.hip).  Every sum has a fixed order: graph replay equals eager bit for bit.
-#include "common.h"
+// k = l of the block (r * r <= 64).  Per-pixel loss definitions, clipping constants and masking are loss_term's and
+// label_valid's (csrc/head_common.h).  Every sum has a fixed order: graph replay equals eager bit for bit.
+#include "head_common.h"
 
 namespace {
 
@@ -14,38 +14,6 @@ struct NHeadParams {
   int h, w, C, H, W, r, cp;
   long long total;                   // N * h * w logit pixels
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// softmax of the logit vector at zp over the wave: this lane's four probabilities (0 for classes >= C)
-__device__ __forceinline__ float4 wave_softmax(const float* zp, int lane, int C, int cp) {
-  const int c0 = lane * 4;
-  float4 v = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
-  if (c0 < cp) v = ld4(zp + c0);
-  const bool i0 = c0 < C, i1 = c0 + 1 < C, i2 = c0 + 2 < C, i3 = c0 + 3 < C;
-  float mx = fmaxf(fmaxf(i0 ? v.x : -3.0e38f, i1 ? v.y : -3.0e38f), fmaxf(i2 ? v.z : -3.0e38f, i3 ? v.w : -3.0e38f));
-  mx = wave_max(mx);
-  const float4 e = make_float4(i0 ? __expf(v.x - mx) : 0.f, i1 ? __expf(v.y - mx) : 0.f, i2 ? __expf(v.z - mx) : 0.f,
-                               i3 ? __expf(v.w - mx) : 0.f);
-  const float inv = 1.f / wave_sum((e.x + e.y) + (e.z + e.w));
-  return make_float4(e.x * inv, e.y * inv, e.z * inv, e.w * inv);
-}
-
-__device__ __forceinline__ void pixel_of(long long s, int w, int h, int* x, int* y, long long* n) {
-  *x = (int)(s % w);
-  const long long t = s / w;
-  *y = (int)(t % h);
-  *n = t / h;
-}
 
 // ------------------------------------------------------------------------------ loss and d loss / d z
 __global__ __launch_bounds__(256) void nearest_head_train_kernel(NHeadParams p) {
@@ -67,31 +35,11 @@ __global__ __launch_bounds__(256) void nearest_head_train_kernel(NHeadParams p) 
       lab = (int)p.labels[f];
       if (p.pixel_w) swt = p.pixel_w[f];
     }
-    const bool masked = p.ignore_index != 0 && lab == p.ignore_index;   // loss.py:139 truthiness
-    const bool valid = lane < rr && !masked && lab >= 0 && lab < p.C;
+    const bool valid = lane < rr && label_valid(lab, p.ignore_index, p.C);
     if (!valid) lab = -1;
-    // p_t: component lab & 3 of the lane lab >> 2
-    const int src = valid ? (lab >> 2) : 0;
-    const float q0 = __shfl(pr.x, src), q1 = __shfl(pr.y, src), q2 = __shfl(pr.z, src), q3 = __shfl(pr.w, src);
-    const int comp = lab & 3;
-    const float pt = valid ? (comp == 0 ? q0 : comp == 1 ? q1 : comp == 2 ? q2 : q3) : 1.f;
+    const float pt = wave_label_prob(pr, valid, lab);
     float l, f;
-    if (p.loss_kind == DL3P_LOSS_WEIGHTED_CE) {
-      const float wy = valid ? p.class_w[lab] : 0.f;
-      l = -wy * logf(pt);
-      f = wy;
-    } else if (p.loss_kind == DL3P_LOSS_FOCAL) {
-      const float pc = fmaxf(pt, 1e-15f);                  // 1 - 1e-15 rounds to 1 in fp32: the upper clip is a no-op
-      const float om = 1.f - pc, lp = logf(pc);
-      const float pw1 = om > 0.f ? powf(om, p.focal_gamma - 1.f) : (p.focal_gamma == 1.f ? 1.f : 0.f);
-      const float pw = pw1 * om;
-      l = -p.focal_alpha * pw * lp;
-      f = pt >= 1e-15f ? p.focal_alpha * (pw - p.focal_gamma * pw1 * pc * lp) : 0.f;
-    } else {
-      const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
-      l = -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-      f = unclipped ? 1.f : 0.f;
-    }
+    loss_term(p.loss_kind, pt, valid, lab, p.class_w, p.focal_gamma, p.focal_alpha, &l, &f);
     l *= swt;
     f *= swt;
     loss += wave_sum(valid ? l : 0.f);
@@ -172,11 +120,7 @@ __device__ __forceinline__ int argmax_of(const float* zp, int C, int cp) {
 // one thread per logit pixel; integer counts (LDS histogram for C <= 64, 64-bit atomics otherwise): any order gives the same matrix
 __global__ __launch_bounds__(256) void nearest_argmax_confusion_kernel(NEvalParams p) {
   extern __shared__ unsigned int hist[];                 // [C][C], only with labels and C <= 64
-  const bool use_lds = p.labels && p.cm && p.C <= 64;
-  if (use_lds) {
-    for (int i = threadIdx.x; i < p.C * p.C; i += 256) hist[i] = 0u;
-    __syncthreads();
-  }
+  const ConfusionHist cm = confusion_begin(hist, p.cm, p.C, p.labels && p.cm && p.C <= 64);
   for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
     int x, y;
     long long n;
@@ -186,45 +130,27 @@ __global__ __launch_bounds__(256) void nearest_argmax_confusion_kernel(NEvalPara
       for (int j = 0; j < p.r; ++j) {
         const size_t f = ((size_t)n * p.H + (size_t)y * p.r + i) * p.W + (size_t)x * p.r + j;
         if (p.pred) p.pred[f] = arg;
-        if (p.labels && p.cm) {
-          const int lab = (int)p.labels[f];
-          if (lab >= 0 && lab < p.C) {
-            if (use_lds) atomicAdd(&hist[lab * p.C + arg], 1u);
-            else atomicAdd(&p.cm[(size_t)lab * p.C + arg], 1ull);
-          }
-        }
+        if (p.labels && p.cm) cm.count((int)p.labels[f], arg);
       }
   }
-  if (use_lds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < p.C * p.C; i += 256)
-      if (hist[i]) atomicAdd(&p.cm[i], (unsigned long long)hist[i]);
-  }
+  cm.flush();
 }
 
 // counts[n][3][C] (see dl3p_class_counts): workgroups stay inside one image and keep an LDS histogram
 __global__ __launch_bounds__(256) void nearest_class_counts_kernel(NEvalParams p, int* counts, int blocks_per_image) {
   extern __shared__ unsigned int hist[];                 // [3][C]
-  for (int i = threadIdx.x; i < 3 * p.C; i += 256) hist[i] = 0u;
-  __syncthreads();
+  const ClassCountHist cc = class_counts_begin(hist, p.C);
   const int n = blockIdx.x / blocks_per_image, b = blockIdx.x - n * blocks_per_image;
   const int hw = p.h * p.w;
   for (int s = b * 256 + threadIdx.x; s < hw; s += blocks_per_image * 256) {
     const int x = s % p.w, y = s / p.w;
     const int arg = argmax_of(p.z + ((size_t)n * hw + s) * p.ldz, p.C, p.cp);
-    atomicAdd(&hist[2 * p.C + arg], (unsigned int)(p.r * p.r));
+    cc.predicted(arg, (unsigned int)(p.r * p.r));
     for (int i = 0; i < p.r; ++i)
-      for (int j = 0; j < p.r; ++j) {
-        const int lab = (int)p.labels[((size_t)n * p.H + (size_t)y * p.r + i) * p.W + (size_t)x * p.r + j];
-        if (lab >= 0 && lab < p.C) {
-          atomicAdd(&hist[p.C + lab], 1u);
-          if (lab == arg) atomicAdd(&hist[lab], 1u);
-        }
-      }
+      for (int j = 0; j < p.r; ++j)
+        cc.labelled((int)p.labels[((size_t)n * p.H + (size_t)y * p.r + i) * p.W + (size_t)x * p.r + j], arg);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * p.C; i += 256)
-    if (hist[i]) atomicAdd(&counts[(size_t)n * 3 * p.C + i], (int)hist[i]);
+  cc.flush(counts + (size_t)n * 3 * p.C);
 }
 
 // the scale r with (H, W) = r (h, w), or 0

@@ -9,21 +9,8 @@
 //   t = src - floor(src).
 // HBM-bound; NHWC with 16-B channel vectors where C % 4 == 0.  The backward is the transposed
 // operator in gather form (each input pixel sums the output pixels that read it) -> no atomics.
-#include "common.h"
+#include "head_common.h"
 #include <stdlib.h>
-
-// exp of the max-shifted logits is the hardware v_exp_f32 (1 ulp on the [-87, 0] arguments a softmax sees); the
-// full-range expf costs ~25 instructions x 21 classes per pixel and made the head kernels VALU-bound
-struct Lerp { int lo, hi; float t; };
-__host__ __device__ __forceinline__ Lerp lerp_coeff(int o, float scale, int in_size) {
-  const float src = ((float)o + 0.5f) * scale - 0.5f;
-  const float fl = floorf(src);
-  Lerp r;
-  r.lo = max((int)fl, 0);
-  r.hi = min((int)ceilf(src), in_size - 1);
-  r.t = src - fl;
-  return r;
-}
 
 struct ResizeParams {
   const float* x; int ldx; float* y; int ldy;
@@ -55,12 +42,7 @@ __global__ __launch_bounds__(256) void resize_fwd_kernel(ResizeParams p) {
     const float4 tr = ld4(img + ((size_t)ly.lo * p.w + lx.hi) * p.ldx);
     const float4 bl = ld4(img + ((size_t)ly.hi * p.w + lx.lo) * p.ldx);
     const float4 br = ld4(img + ((size_t)ly.hi * p.w + lx.hi) * p.ldx);
-    // TF: top = tl + (tr-tl)*tx; bottom = bl + (br-bl)*tx; out = top + (bottom-top)*ty
-    float4 o;
-#define LERP2(f) { float top = tl.f + (tr.f - tl.f) * lx.t; float bot = bl.f + (br.f - bl.f) * lx.t; o.f = top + (bot - top) * ly.t; }
-    LERP2(x) LERP2(y) LERP2(z) LERP2(w)
-#undef LERP2
-    st4(p.y + (((size_t)n * p.H + oy) * p.W + ox) * p.ldy + c, o);
+    st4(p.y + (((size_t)n * p.H + oy) * p.W + ox) * p.ldy + c, lerp2(tl, tr, bl, br, lx.t, ly.t));
   }
 }
 
@@ -119,12 +101,8 @@ __global__ __launch_bounds__(256) void resize_fwd_seg_kernel(ResizeParams p) {
       const float t = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.t), j));
       const float4 tl = ld4(tile + lo * 256), tr = ld4(tile + hi * 256);
       const float4 bl = ld4(tile + (RS_NCOL + lo) * 256), br = ld4(tile + (RS_NCOL + hi) * 256);
-      float4 o;
-#define LERP2(f) { float tp = tl.f + (tr.f - tl.f) * t; float bt = bl.f + (br.f - bl.f) * t; o.f = tp + (bt - tp) * ly.t; }
-      LERP2(x) LERP2(y) LERP2(z) LERP2(w)
-#undef LERP2
       // a column past the row's end repeats the last pixel (same value, same address): the stores stay unconditional
-      st4(yrow + (size_t)min(ox0 + j, p.W - 1) * p.ldy, o);
+      st4(yrow + (size_t)min(ox0 + j, p.W - 1) * p.ldy, lerp2(tl, tr, bl, br, t, ly.t));
     }
   }
 }
@@ -327,7 +305,6 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams p) {
   __shared__ __attribute__((aligned(16))) float tr_s[4][64 * (CP + 4)];
   float* trw = tr_s[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63;
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
   float loss = 0.f;
   // whole waves stay in the loop (lanes past the end recompute the last pixel and store nothing): the
   // coalesced gradient store below needs every lane of the wave
@@ -338,31 +315,11 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams p) {
     const int row = s / p.W;
     const int oy = row % p.H;
     const int n = row / p.H;
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
-    float v[CP];
+    float v[CP], e[CP];
+    tap_logits<CP>(v, Taps(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W));
 #pragma unroll
-    for (int c4 = 0; c4 < CP / 4; ++c4) {
-      const float4 tl = ld4(ptl + c4 * 4), tr = ld4(ptr + c4 * 4), bl = ld4(pbl + c4 * 4), br = ld4(pbr + c4 * 4);
-#define LERP2(f, i) { float top = tl.f + (tr.f - tl.f) * lx.t; float bot = bl.f + (br.f - bl.f) * lx.t; v[c4 * 4 + i] = top + (bot - top) * ly.t; }
-      LERP2(x, 0) LERP2(y, 1) LERP2(z, 2) LERP2(w, 3)
-#undef LERP2
-    }
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int c = 0; c < CP; ++c) if (c < p.C) mx = fmaxf(mx, v[c]);
-    float e[CP];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < CP; ++c) {
-      e[c] = c < p.C ? __expf(v[c] - mx) : 0.f;
-      sum += e[c];
-    }
-    const float inv = 1.f / sum;
+    for (int c = 0; c < CP; ++c) e[c] = v[c];
+    const float inv = softmax_exp<CP>(e, p.C);
     const size_t obase = (size_t)s * p.C;
     const size_t bbase = (size_t)s * p.ld_big;
     const bool vec = p.ld_big == CP;   // padded rows: 16-B stores, pad channels written as 0
@@ -383,34 +340,12 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams p) {
     }
     if (p.labels) {
       const int lab = (int)p.labels[s];
-      const bool masked = p.ignore_index != 0 && lab == p.ignore_index;   // loss.py:139 truthiness
-      const bool valid = !masked && lab >= 0 && lab < p.C;
+      const bool valid = label_valid(lab, p.ignore_index, p.C);
       float pt = 0.f;
 #pragma unroll
       for (int c = 0; c < CP; ++c) if (c == lab) pt = e[c] * inv;
-      // per-pixel loss l(p_t) and the factor f with d l / d z_c = f * (p_c - [c == y]):
-      //   cross entropy (loss.py:121-156)   l = -log(clip(p_t, 1e-7, 1 - 1e-7)),  f = 1 inside the clip range, else 0
-      //   class-weighted  (loss.py:159-191) l = -w_y log(p_t)  (no clipping),      f = w_y
-      //   focal           (loss.py:63-118)  l = -alpha (1 - p_t)^gamma log(p_t),   p_t clipped to [1e-15, 1 - 1e-15];
-      //                                     f = alpha ((1 - p_t)^gamma - gamma (1 - p_t)^(gamma - 1) p_t log p_t)
       float li, f;
-      if (p.loss_kind == DL3P_LOSS_WEIGHTED_CE) {
-        float wy = 0.f;
-        if (valid) wy = p.class_w[lab];
-        li = -wy * logf(pt);
-        f = wy;
-      } else if (p.loss_kind == DL3P_LOSS_FOCAL) {
-        const float pc = fmaxf(pt, 1e-15f);               // 1 - 1e-15 rounds to 1 in fp32: the upper clip is a no-op
-        const float om = 1.f - pc, lp = logf(pc);
-        const float pw1 = om > 0.f ? powf(om, p.focal_gamma - 1.f) : (p.focal_gamma == 1.f ? 1.f : 0.f);
-        const float pw = pw1 * om;
-        li = -p.focal_alpha * pw * lp;
-        f = pt >= 1e-15f ? p.focal_alpha * (pw - p.focal_gamma * pw1 * pc * lp) : 0.f;
-      } else {
-        const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
-        li = -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-        f = unclipped ? 1.f : 0.f;
-      }
+      loss_term(p.loss_kind, pt, valid, lab, p.class_w, p.focal_gamma, p.focal_alpha, &li, &f);
       if (p.pixel_w) {            // the weighted per-pixel losses are averaged over ALL entries, like the unweighted ones
         const float sw = p.pixel_w[s];
         li *= sw;
@@ -453,62 +388,29 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams p) {
   }
 }
 
-// More than 32 classes (the reference allows up to 253: train.py:34): a pixel's class vector no longer fits registers.
-// One thread per output pixel walks the classes three times (maximum, sum of exponentials, outputs), re-interpolating
-// each logit from its 4 neighbours (L1 / L2 hits); same arithmetic as head_kernel, class by class.
+// More than 32 classes: one thread per output pixel walks the classes (softmax_walk), then once more for the outputs.
 __global__ __launch_bounds__(256) void head_kernel_big(HeadParams p) {
   __shared__ float wsum[4];
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
   float loss = 0.f;
   for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
-    const int ox = s % p.W;
-    const long long row = s / p.W;
-    const int oy = (int)(row % p.H), n = (int)(row / p.H);
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
-    auto logit = [&](int c) {
-      const float top = ptl[c] + (ptr[c] - ptl[c]) * lx.t, bot = pbl[c] + (pbr[c] - pbl[c]) * lx.t;
-      return top + (bot - top) * ly.t;
-    };
-    float mx = -3.0e38f;
-    for (int c = 0; c < p.C; ++c) mx = fmaxf(mx, logit(c));
-    float sum = 0.f;
-    for (int c = 0; c < p.C; ++c) sum += __expf(logit(c) - mx);
-    const float inv = 1.f / sum;
+    int ox, oy;
+    long long n;
+    pixel_of(s, p.W, p.H, &ox, &oy, &n);
+    const SoftmaxWalk k = softmax_walk(Taps(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W), p.C);
     const int lab = p.labels ? (int)p.labels[s] : -1;
-    const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-    const bool valid = p.labels && !masked && lab >= 0 && lab < p.C;
+    const bool valid = p.labels && label_valid(lab, p.ignore_index, p.C);
     float li = 0.f, f = 0.f;
     if (p.labels) {
-      const float pt = valid ? __expf(logit(lab) - mx) * inv : 0.f;
-      if (p.loss_kind == DL3P_LOSS_WEIGHTED_CE) {
-        const float wy = valid ? p.class_w[lab] : 0.f;
-        li = -wy * logf(pt);
-        f = wy;
-      } else if (p.loss_kind == DL3P_LOSS_FOCAL) {
-        const float pc = fmaxf(pt, 1e-15f);
-        const float om = 1.f - pc, lp = logf(pc);
-        const float pw1 = om > 0.f ? powf(om, p.focal_gamma - 1.f) : (p.focal_gamma == 1.f ? 1.f : 0.f);
-        const float pw = pw1 * om;
-        li = -p.focal_alpha * pw * lp;
-        f = pt >= 1e-15f ? p.focal_alpha * (pw - p.focal_gamma * pw1 * pc * lp) : 0.f;
-      } else {
-        const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
-        li = -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-        f = unclipped ? 1.f : 0.f;
-      }
+      const float pt = valid ? k.prob(lab) : 0.f;
+      loss_term(p.loss_kind, pt, valid, lab, p.class_w, p.focal_gamma, p.focal_alpha, &li, &f);
       if (p.pixel_w) { const float sw = p.pixel_w[s]; li *= sw; f *= sw; }
       if (valid) loss += li;
     }
     const float gs = valid ? f * p.inv_count : 0.f;
     for (int c = 0; c < p.ld_big; ++c) {
       const bool in = c < p.C;
-      const float v = in ? logit(c) : 0.f;
-      const float pr = in ? __expf(v - mx) * inv : 0.f;
+      const float v = in ? tap_logit(k.t, c) : 0.f;
+      const float pr = in ? k.exp_of(v) * k.inv : 0.f;
       if (p.logits_big) p.logits_big[(size_t)s * p.ld_big + c] = v;
       if (p.dlogits) p.dlogits[(size_t)s * p.ld_big + c] = in ? gs * (pr - (c == lab ? 1.f : 0.f)) : 0.f;
       if (p.probs && in) p.probs[(size_t)s * p.C + c] = pr;
@@ -592,75 +494,28 @@ struct EvalParams {
 template <int CP>
 __global__ __launch_bounds__(256) void argmax_confusion_kernel(EvalParams p) {
   extern __shared__ unsigned int hist[];                 // [C][C], only with labels and C <= 64
-  const bool use_lds = p.labels && p.cm && p.C <= 64;
-  if (use_lds) {
-    for (int i = threadIdx.x; i < p.C * p.C; i += 256) hist[i] = 0u;
-    __syncthreads();
-  }
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
+  const ConfusionHist cm = confusion_begin(hist, p.cm, p.C, p.labels && p.cm && p.C <= 64);
   for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
     const int ox = s % p.W;
     const int row = s / p.W;
     const int oy = row % p.H;
     const int n = row / p.H;
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
-    float best = -3.0e38f;
-    int arg = 0;
-#pragma unroll
-    for (int c4 = 0; c4 < CP / 4; ++c4) {
-      const float4 tl = ld4(ptl + c4 * 4), tr = ld4(ptr + c4 * 4), bl = ld4(pbl + c4 * 4), br = ld4(pbr + c4 * 4);
-      // the same arithmetic as head_kernel, so predict() followed by a host argmax gives the same class
-#define LERP2(f, i) { float top = tl.f + (tr.f - tl.f) * lx.t; float bot = bl.f + (br.f - bl.f) * lx.t; \
-                      const float v = top + (bot - top) * ly.t; \
-                      if (c4 * 4 + i < p.C && v > best) { best = v; arg = c4 * 4 + i; } }
-      LERP2(x, 0) LERP2(y, 1) LERP2(z, 2) LERP2(w, 3)
-#undef LERP2
-    }
+    const int arg = argmax_taps<CP>(Taps(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W), p.C);
     if (p.pred) p.pred[s] = arg;
-    if (p.labels && p.cm) {
-      const int lab = (int)p.labels[s];
-      if (lab >= 0 && lab < p.C) {
-        if (use_lds) atomicAdd(&hist[lab * p.C + arg], 1u);
-        else atomicAdd(&p.cm[(size_t)lab * p.C + arg], 1ull);
-      }
-    }
+    if (p.labels && p.cm) cm.count((int)p.labels[s], arg);
   }
-  if (use_lds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < p.C * p.C; i += 256)
-      if (hist[i]) atomicAdd(&p.cm[i], (unsigned long long)hist[i]);
-  }
+  cm.flush();
 }
 
 __global__ __launch_bounds__(256) void argmax_confusion_big(EvalParams p) {
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
+  const ConfusionHist cm = confusion_begin(nullptr, p.cm, p.C, false);
   for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < p.total; s += (long long)gridDim.x * 256) {
-    const int ox = s % p.W;
-    const long long row = s / p.W;
-    const int oy = (int)(row % p.H), n = (int)(row / p.H);
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
-    float best = -3.0e38f;
-    int arg = 0;
-    for (int c = 0; c < p.C; ++c) {
-      const float top = ptl[c] + (ptr[c] - ptl[c]) * lx.t, bot = pbl[c] + (pbr[c] - pbl[c]) * lx.t;
-      const float v = top + (bot - top) * ly.t;
-      if (v > best) { best = v; arg = c; }
-    }
+    int ox, oy;
+    long long n;
+    pixel_of(s, p.W, p.H, &ox, &oy, &n);
+    const int arg = argmax_walk(Taps(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W), p.C);
     if (p.pred) p.pred[s] = arg;
-    if (p.labels && p.cm) {
-      const int lab = (int)p.labels[s];
-      if (lab >= 0 && lab < p.C) atomicAdd(&p.cm[(size_t)lab * p.C + arg], 1ull);
-    }
+    if (p.labels && p.cm) cm.count((int)p.labels[s], arg);
   }
 }
 
@@ -704,36 +559,16 @@ extern "C" int dl3p_argmax_confusion(const float* z, int ldz, const float* label
 // counts[n][3][C] (int32, zeroed by the caller): workgroups stay inside one image and keep an LDS histogram.
 __global__ __launch_bounds__(256) void class_counts_kernel(EvalParams p, int* counts, int blocks_per_image) {
   extern __shared__ unsigned int hist[];                 // [3][C]
-  for (int i = threadIdx.x; i < 3 * p.C; i += 256) hist[i] = 0u;
-  __syncthreads();
+  const ClassCountHist cc = class_counts_begin(hist, p.C);
   const int n = blockIdx.x / blocks_per_image, b = blockIdx.x - n * blocks_per_image;
   const int HW = p.H * p.W;
-  const float sy = (float)p.h / (float)p.H, sx = (float)p.w / (float)p.W;
-  const float* img = p.z + (size_t)n * p.h * p.w * p.ldz;
   for (int s = b * 256 + threadIdx.x; s < HW; s += blocks_per_image * 256) {
     const int ox = s % p.W, oy = s / p.W;
-    const Lerp ly = lerp_coeff(oy, sy, p.h), lx = lerp_coeff(ox, sx, p.w);
-    const float* ptl = img + ((size_t)ly.lo * p.w + lx.lo) * p.ldz;
-    const float* ptr = img + ((size_t)ly.lo * p.w + lx.hi) * p.ldz;
-    const float* pbl = img + ((size_t)ly.hi * p.w + lx.lo) * p.ldz;
-    const float* pbr = img + ((size_t)ly.hi * p.w + lx.hi) * p.ldz;
-    float best = -3.0e38f;
-    int arg = 0;
-    for (int c = 0; c < p.C; ++c) {                      // same arithmetic as head_kernel / argmax_confusion_kernel
-      const float top = ptl[c] + (ptr[c] - ptl[c]) * lx.t, bot = pbl[c] + (pbr[c] - pbl[c]) * lx.t;
-      const float v = top + (bot - top) * ly.t;
-      if (v > best) { best = v; arg = c; }
-    }
-    const int lab = (int)p.labels[(size_t)n * HW + s];
-    atomicAdd(&hist[2 * p.C + arg], 1u);
-    if (lab >= 0 && lab < p.C) {
-      atomicAdd(&hist[p.C + lab], 1u);
-      if (lab == arg) atomicAdd(&hist[lab], 1u);
-    }
+    const int arg = argmax_walk(Taps(p.z, p.ldz, n, oy, ox, p.h, p.w, p.H, p.W), p.C);
+    cc.predicted(arg, 1u);
+    cc.labelled((int)p.labels[(size_t)n * HW + s], arg);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * p.C; i += 256)
-    if (hist[i]) atomicAdd(&counts[(size_t)n * 3 * p.C + i], (int)hist[i]);
+  cc.flush(counts + (size_t)n * 3 * p.C);
 }
 
 extern "C" int dl3p_class_counts(const float* z, int ldz, const float* labels, int32_t* counts, int N, int h, int w,
@@ -852,30 +687,18 @@ __global__ __launch_bounds__(512) void head_train_kernel(HeadTrainParams p) {
       for (int c4 = 0; c4 < C4; ++c4) {
         const float4 tl = *reinterpret_cast<const float4*>(ptl + c4 * 4), tr = *reinterpret_cast<const float4*>(ptr + c4 * 4);
         const float4 bl = *reinterpret_cast<const float4*>(pbl + c4 * 4), br = *reinterpret_cast<const float4*>(pbr + c4 * 4);
-#define LERP2(f, i) { float top = tl.f + (tr.f - tl.f) * lx.t; float bot = bl.f + (br.f - bl.f) * lx.t; v[c4 * 4 + i] = top + (bot - top) * ly.t; }
-        LERP2(x, 0) LERP2(y, 1) LERP2(z, 2) LERP2(w, 3)
-#undef LERP2
+        const float4 o = lerp2(tl, tr, bl, br, lx.t, ly.t);
+        v[c4 * 4] = o.x; v[c4 * 4 + 1] = o.y; v[c4 * 4 + 2] = o.z; v[c4 * 4 + 3] = o.w;
       }
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) if (c < p.C) mx = fmaxf(mx, v[c]);
-      float sum = 0.f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) {
-        v[c] = c < p.C ? __expf(v[c] - mx) : 0.f;
-        sum += v[c];
-      }
-      const float inv = 1.f / sum;
+      const float inv = softmax_exp<CP>(v, p.C);
       const int lab = (int)p.labels[((size_t)n * p.H + oy) * p.W + ox];
-      const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-      const bool valid = !masked && lab >= 0 && lab < p.C;
+      const bool valid = label_valid(lab, p.ignore_index, p.C);
       float pt = 0.f;
 #pragma unroll
       for (int c = 0; c < CP; ++c) if (c == lab) pt = v[c] * inv;
-      const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
       const bool owner = ly.lo >= iy0 && ly.lo <= iy1 && lx.lo >= ix0 && lx.lo <= ix1;
-      if (valid && owner) loss += -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-      const float gs = (valid && unclipped) ? p.inv_count : 0.f;
+      if (valid && owner) loss += ce_loss(pt);
+      const float gs = (valid && ce_unclipped(pt)) ? p.inv_count : 0.f;
 #pragma unroll
       for (int c4 = 0; c4 < C4; ++c4) {
         float d[4];
@@ -1164,8 +987,7 @@ __global__ __launch_bounds__(HR_THREADS) void head_xpass_kernel(HeadRowsParams p
       for (int c2 = 2; c2 < CP / 2; c2 += 2) { s2 += v[c2]; s3 += v[c2 + 1]; }
       s2 += s3;
       const float inv = 1.f / (s2[0] + s2[1]);
-      const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-      const bool valid = !masked && lab >= 0 && lab < p.C;
+      const bool valid = label_valid(lab, p.ignore_index, p.C);
       // the label's probability: its logit again from LDS (the same expressions -> the same bits) instead of a 24-way select
       float pt = 0.f;
       if (valid) {
@@ -1173,9 +995,8 @@ __global__ __launch_bounds__(HR_THREADS) void head_xpass_kernel(HeadRowsParams p
         const float a = top[o], b = bot[o];
         pt = __builtin_amdgcn_exp2f(fmaf(a + (b - a) * ly.t, LOG2E, mneg)) * inv;
       }
-      const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
-      if (valid && own) loss += -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-      const float gs = (valid && unclipped) ? p.inv_count : 0.f;
+      if (valid && own) loss += ce_loss(pt);
+      const float gs = (valid && ce_unclipped(pt)) ? p.inv_count : 0.f;
       const float k = gs * inv;
       const hr_f2 k2 = {k, k};
       float* gpx = gr + X * 4;
@@ -1211,12 +1032,10 @@ __global__ __launch_bounds__(HR_THREADS) void head_xpass_kernel(HeadRowsParams p
 #pragma unroll
       for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
       const float inv = 1.f / sum;
-      const bool masked = p.ignore_index != 0 && lab == p.ignore_index;
-      const bool valid = tail_lane && !masked && lab >= 0 && lab < p.C;
+      const bool valid = tail_lane && label_valid(lab, p.ignore_index, p.C);
       const float pt = valid ? __shfl(e, (lane & 32) + (lab & 31)) * inv : 0.f;
-      const bool unclipped = pt > 1e-7f && pt < 1.f - 1e-7f;
-      if (valid && c == 0 && own_first) loss += -logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
-      const float gs = (valid && unclipped) ? p.inv_count : 0.f;
+      if (valid && c == 0 && own_first) loss += ce_loss(pt);
+      const float gs = (valid && ce_unclipped(pt)) ? p.inv_count : 0.f;
       if (on) gr[o] = c == lab ? gs * (pt - 1.f) : e * (gs * inv);
     }
     lab_cur = (int)lab_req;
