@@ -1044,6 +1044,37 @@ int dl3p_topk_threshold(const float* loss_map, size_t P, double top_k_percent, i
                         int step_bias, int first_histogram_ready, void* workspace, void* record, void* stream);
 int dl3p_mining_weights(const float* loss_map, const float* base, const void* record, float* weights, size_t P, void* stream);
 
+/* ---------------------------------------------------------------- dense CRF post-processing (csrc/crf.hip)
+ * Mean-field inference of the fully connected CRF (unary from a hard class mask, a Gaussian and a bilateral Potts kernel, symmetric
+ * normalisation), every message pass the exact sum out_i = sum_j k(f_i, f_j) V_j over ALL pixels j of the image, j == i included.
+ * n = H*W pixels per image, C <= 32 classes; a class-vector row holds 32 fp32 columns (strides ldq / ldv / ldo >= 32): columns of
+ * absent classes and columns >= C are exactly 0.  Batch is a grid dimension, offsets are 64-bit, nothing synchronises.
+ * dl3p_crf_unary: ONE launch finds the classes present in mask (N, n) per image (ids outside [0, C) are not counted), leaves
+ * census[N][2] = {bit mask of the present classes, n_labels} and writes Q0 = softmax(-U): U = -log(gt_prob) at the pixel's own class,
+ * -log((1 - gt_prob) / (n_labels - 1)) at every other present class, +inf at an absent one.
+ * dl3p_crf_gauss_norm: norm[n] = 1 / sqrt(sum_j k(i, j) + 1e-20) of the Gaussian kernel exp(-dx^2 / (2 sx^2) - dy^2 / (2 sy^2)), the
+ * same for every image.  dl3p_crf_gauss_message: out = sum_j k(i, j) scale[j] V_j by a row pass into tmp (N, n, 32) and a column pass,
+ * both over the full width / height (no truncated window); scale[n] or NULL.  V rows 16-byte aligned, ldv % 4 == 0.
+ * dl3p_crf_bilateral_message: the same sum for k = exp(-(dx^2 + dy^2) / (2 sxy^2) - |d rgb|^2 / (2 srgb^2)) of the uint8 image
+ * (N, n, 3) through v_mfma_f32_32x32x2_f32; scale (N, n) or NULL.  v NULL: V is the unit column 0, and norm_out (N, n) receives
+ * 1 / sqrt(column 0 + 1e-20) (out may be NULL then).  Sides up to 2048: the squared distances are exact in fp32.
+ * dl3p_crf_update: Q = softmax over the present classes of -U + weight_g norm_g[i] fg_i + weight_b norm_b[i] fb_i (fg / fb may be NULL:
+ * that term is absent), written to q if q is not NULL; mask_out (N, n), if not NULL, receives argmax Q with the lowest class id on
+ * ties, or the input mask where the image has fewer than two present classes.  q may be the buffer fg / fb were computed from.
+ * dl3p_mask_confusion: confusion[label * C + mask] += 1 for 0 <= label, mask < C (C <= 64), dl3p_argmax_confusion's counters for a mask
+ * that exists already.  dl3p_denormalize_u8: out = (uint8) clamp(x * 127.5 + 127.5, 0, 255), truncated. */
+int dl3p_crf_unary(const int* mask, int32_t* census, float* q, int ldq, float gt_prob, int N, int n, int C, void* stream);
+int dl3p_crf_gauss_norm(float* norm, int H, int W, float sx, float sy, void* stream);
+int dl3p_crf_gauss_message(const float* v, int ldv, const float* scale, float* tmp, float* out, int ldo, int N, int H, int W, float sx,
+                           float sy, void* stream);
+int dl3p_crf_bilateral_message(const unsigned char* img, const float* v, int ldv, const float* scale, float* out, int ldo,
+                               float* norm_out, int N, int H, int W, float sxy, float srgb, void* stream);
+int dl3p_crf_update(const int* mask, const int* census, const float* fg, const float* norm_g, const float* fb, const float* norm_b,
+                    float weight_g, float weight_b, float gt_prob, float* q, int ldq, int32_t* mask_out, int N, int n, int C,
+                    void* stream);
+int dl3p_mask_confusion(const int* pred_mask, const float* labels, unsigned long long* confusion, size_t total, int C, void* stream);
+int dl3p_denormalize_u8(const float* x, unsigned char* out, size_t total, void* stream);
+
 /* ---------------------------------------------------------------- measurement hook
  * dl3p_probe_arm(i): the NEXT depthwise-forward or pointwise-GEMM kernel launch of the calling thread is issued with a pair of HIP
  * events (hipExtLaunchKernelGGL start/stop events on the launch stream) stored in slot i (0 <= i < 4096);

@@ -12,14 +12,18 @@ The overlay is NOT the reference's picture: visualize_segmentation (common/utils
 1000 x 1000 canvas with a legend.  What is kept is its per-pixel composite `imshow(image); imshow(mask_image, alpha=overlay)` at the
 frame's own resolution, as the integer rule (img (256 - A) + colour A + 128) >> 8 with A = rint(overlay * 256).
 
-Not built: dense-CRF post-processing (`do_crf=True` raises), `segment_video` and the argparse `main` (they need cv2's capture and
-window), `dump_saved_model` (TensorFlow's SavedModel)."""
+Dense-CRF post-processing runs on the device between the class ids and the resize back to the frame (`dense_crf=True`, ops.dense_crf:
+the reference's crf_postprocess with every filter computed exactly).  `do_crf=True` still raises: that switch names pydensecrf's
+permutohedral-lattice approximation, which is not built.
+
+Not built: the lattice approximation behind `do_crf`, `segment_video` and the argparse `main` (they need cv2's capture and window),
+`dump_saved_model` (TensorFlow's SavedModel)."""
 import functools
 import os
 
 import numpy as np
 
-from . import augment
+from . import augment, ops
 from ._lib import lib
 from .model import batch_input, get_deeplabv3p_model, get_fast_scnn_model, get_unet_model, single_pass
 
@@ -119,7 +123,8 @@ def mask_resize(mask, target_size):
 
 class DeepLab(object):
     """deeplab.py:43-113 with the reference's keyword arguments.  `weights_path=None` builds a randomly initialised model (the
-    reference cannot); `do_crf=True` raises: the dense-CRF post-processing is not built."""
+    reference cannot); `dense_crf=True` (or a dict of ops.dense_crf's keyword arguments) refines every mask with the exact dense CRF on
+    the device; `do_crf=True` raises: pydensecrf's lattice approximation is not built."""
     _defaults = {
         'model_type': 'mobilenetv2_lite',
         'classes_path': os.path.join('configs', 'voc_classes.txt'),
@@ -131,18 +136,33 @@ class DeepLab(object):
         # single unmirrored pass
         'scales': (1.0,),
         'flip': False,
+        # the fully connected CRF on the device (ops.dense_crf): False, True (the reference's parameters) or a dict of its keywords
+        'dense_crf': False,
     }
 
     def __init__(self, **kwargs):
         for key, value in {**self._defaults, **kwargs}.items():       # (keys beyond the defaults are kept as attributes, as there)
             setattr(self, key, value)
         if self.do_crf:
-            raise ValueError('do_crf=True: the dense-CRF post-processing (deeplabv3p/postprocess_np.py) is not built')
+            raise ValueError('do_crf=True names the CRF of deeplabv3p/postprocess_np.py as pydensecrf filters it, on a permutohedral '
+                             'lattice; that approximation is not built.  dense_crf=True runs the same CRF with exact filters on the '
+                             'device')
         self.model_input_shape = tuple(int(v) for v in self.model_input_shape)
         self.class_names = get_classes(self.classes_path)
+        self.crf_params = ops.crf_params(self.dense_crf, len(self.class_names))     # (refused before the model is built)
         self.deeplab_model = self._generate_model()
         if not single_pass(self.scales, self.flip):
             self.scales = self.deeplab_model.tta_scales(self.scales)
+
+    def _refine(self, pred, x):
+        """the dense CRF over the class ids `pred` (N, H, W) with the images `x` at the model's size: CUDA bytes, or normalised
+        float32 that go back to bytes by the reference's denormalize_image"""
+        import torch
+        if self.crf_params is None:
+            return pred
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8):
+            x = ops.denormalize_u8(torch.as_tensor(np.asarray(x, dtype=np.float32)).cuda(non_blocking=True))
+        return ops.dense_crf(x, pred, len(self.class_names), **self.crf_params)
 
     def _generate_model(self):
         num_classes = len(self.class_names)
@@ -175,7 +195,8 @@ class DeepLab(object):
         frames = _device_u8(frames)
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError('segment_batch takes (N, h, w, 3) 8-bit RGB frames, got shape %r' % (tuple(frames.shape),))
-        pred = self._class_ids(augment.pil_resize(frames, self.model_input_shape))
+        x = augment.pil_resize(frames, self.model_input_shape)
+        pred = self._refine(self._class_ids(x), x)
         return _mask_overlay(pred, frames, len(self.class_names), tuple(frames.shape[1:3]))
 
     def predict(self, image_data, image_shape):
@@ -186,7 +207,7 @@ class DeepLab(object):
         x = batch_input(image_data)
         if isinstance(x, np.ndarray) and x.dtype == np.uint8:       # (bytes on the host go up as bytes)
             x = _device_u8(x)
-        pred = self._class_ids(x)
+        pred = self._refine(self._class_ids(x), x)
         masks, _ = _mask_overlay(pred, None, len(self.class_names), (int(image_shape[0]), int(image_shape[1])))
         return masks[0].cpu().numpy()
 

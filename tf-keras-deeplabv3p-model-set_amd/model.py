@@ -612,15 +612,35 @@ class DeeplabModel:
         self.last_val_metrics = {'Jaccard': float(np.nanmean(jac))} if jac else {}
         return tot / max(cnt, 1)
 
-    def evaluate_miou(self, gen, steps=None, class_names=None, verbose=0, *, scales=(1.0,), flip=False):
+    def evaluate_miou(self, gen, steps=None, class_names=None, verbose=0, *, scales=(1.0,), flip=False, dense_crf=False):
         """eval.py:376-512 `eval_mIOU` for a generator of (images, labels) batches: inference forward, argmax and the
         confusion matrix stay on the device (Executor.eval_step); only the C x C counters come back.  -> miou_from_confusion.
         With other `scales` / `flip` than the defaults DeepLab's multi-scale / mirrored protocol (not the reference repository's: eval.py
         evaluates one scale): per batch every pass's logits are added as probabilities into one running sum on the device and the last
-        launch counts against the labels.  The generator then yields uint8 images"""
+        launch counts against the labels.  The generator then yields uint8 images.
+        dense_crf (True, or a dict of ops.dense_crf's keyword arguments; eval.py --do_crf with exact filters): each batch's class ids,
+        of the single pass or of the multi-scale passes, are refined by the dense CRF on the device with the batch's own images, which
+        the generator yields as uint8, and the refined masks are counted against the labels"""
         import torch
+        from . import ops
         C = self.num_classes
-        if single_pass(scales, flip):
+        crf = ops.crf_params(dense_crf, C)
+        if crf is not None:
+            single = single_pass(scales, flip)
+            if not single:
+                scales = self.tta_scales(scales)
+            H, W = self.input_shape_hw
+            cm = None
+            for base, frames in self._eval_batches(gen, steps, images=self._tta_frames):
+                if cm is None:
+                    cm = torch.zeros((C, C), dtype=torch.int64, device='cuda')
+                if single:
+                    pred = torch.empty((int(frames.shape[0]), H, W), dtype=torch.int32, device='cuda')
+                    base.eval_step(None, pred)
+                else:
+                    pred = self._tta_run(frames, scales, flip, want_mask=True)[1]
+                ops.mask_confusion(ops.dense_crf(frames, pred, C, **crf), base.labels, C, cm)
+        elif single_pass(scales, flip):
             cm = torch.zeros(C * C, dtype=torch.int64, device='cuda')
             for ex, _ in self._eval_batches(gen, steps):
                 ex.eval_step(cm)

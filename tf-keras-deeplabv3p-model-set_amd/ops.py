@@ -1486,3 +1486,135 @@ def mining_weights(loss_map, record, base=None, out=None):
         out = torch.empty_like(loss_map)
     lib().mining_weights(_p(loss_map), _p(base), _p(record), _p(out), loss_map.numel(), _stream())
     return out
+
+
+# ---- dense CRF post-processing (csrc/crf.hip) ----------------------------------------------------------------
+CRF_LP = 32                 # columns of a class-vector row: the column count of v_mfma_f32_32x32x2_f32
+CRF_MAX_CLASSES = 32
+_crf_ws = {}                # (device index, N, H, W) -> the buffers of dense_crf, reused by the next call at that size
+
+
+def crf_check_classes(num_classes):
+    """ValueError where the CRF is asked for with more classes than a class-vector row holds"""
+    if not 1 <= int(num_classes) <= CRF_MAX_CLASSES:
+        raise ValueError('the dense CRF is built for at most %d classes (C <= %d: one MFMA tile of label columns); got %d'
+                         % (CRF_MAX_CLASSES, CRF_MAX_CLASSES, int(num_classes)))
+    return int(num_classes)
+
+
+CRF_KEYS = ('iterations', 'gt_prob', 'sxy_gaussian', 'compat_gaussian', 'sxy_bilateral', 'srgb', 'compat_bilateral')
+
+
+def crf_params(dense_crf, num_classes):
+    """the `dense_crf` switch of the front ends (False, True or a dict of dense_crf's keyword arguments) -> None without the CRF,
+    else the keyword arguments; ValueError for an unknown key or more classes than the CRF serves"""
+    if not dense_crf:
+        return None
+    params = {} if dense_crf is True else dict(dense_crf)
+    unknown = sorted(set(params) - set(CRF_KEYS))
+    if unknown:
+        raise ValueError('dense_crf takes the keys %s (got %s)' % (', '.join(CRF_KEYS), ', '.join(unknown)))
+    crf_check_classes(num_classes)
+    return params
+
+
+def _crf_images(images_u8):
+    if not (isinstance(images_u8, torch.Tensor) and images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
+            and images_u8.shape[3] == 3):
+        raise Dl3pError('the dense CRF takes (N, H, W, 3) uint8 images on the HIP device')
+    return images_u8.contiguous()
+
+
+def _sxy(s):
+    """pydensecrf's sxy: one number or an (sx, sy) pair"""
+    return (float(s[0]), float(s[1])) if isinstance(s, (tuple, list)) else (float(s), float(s))
+
+
+def crf_messages(images_u8, V, *, sxy_gaussian=(3, 3), sxy_bilateral=80, srgb=13, out=None):
+    """the two raw message sums of the dense CRF, before normalisation and weighting: images (N,H,W,3) uint8, V (N,H,W,ld) or
+    (N,H*W,ld) float32 rows (a channel-slice view of a wider buffer may be passed: the first 32 columns are read)
+    -> (gaussian, bilateral), each (N, H*W, 32): out_i = sum over ALL pixels j of k(i, j) V_j, j == i included.
+    out: a pair of (N, H*W, >= 32) buffers to write into"""
+    img = _crf_images(images_u8)
+    N, H, W, _ = img.shape
+    n = H * W
+    V = V.view(N, n, V.shape[-1])
+    vp, ldv = _pl(V)
+    if V.shape[-1] < CRF_LP:
+        raise Dl3pError('crf_messages: V rows hold %d columns (got %d)' % (CRF_LP, V.shape[-1]))
+    g, b = out if out is not None else (torch.empty((N, n, CRF_LP), dtype=torch.float32, device=img.device) for _ in range(2))
+    gp, ldg = _pl(g)
+    bp, ldb = _pl(b)
+    tmp = torch.empty((N, n, CRF_LP), dtype=torch.float32, device=img.device)
+    sx, sy = _sxy(sxy_gaussian)
+    lib().crf_gauss_message(vp, ldv, None, _p(tmp), gp, ldg, N, H, W, sx, sy, _stream())
+    lib().crf_bilateral_message(_p(img), vp, ldv, None, bp, ldb, None, N, H, W, float(sxy_bilateral), float(srgb), _stream())
+    return g, b
+
+
+def dense_crf(images_u8, masks_i32, num_classes, *, iterations=5, gt_prob=0.7, sxy_gaussian=(3, 3), compat_gaussian=3,
+              sxy_bilateral=80, srgb=13, compat_bilateral=10, want_q=False):
+    """fully connected CRF refinement of hard class masks (the reference's deeplabv3p/postprocess_np.py crf_postprocess with
+    zero_unsure=False, every filter exact instead of pydensecrf's lattice): images (N,H,W,3) uint8 and masks (N,H,W) int32 on the
+    device -> refined masks (N,H,W) int32, and Q (N,H,W,C) float32 with want_q.  A mask with a single class comes back unchanged.
+    Runs on the current stream and does not synchronise; the buffers are kept per (device, N, H, W)"""
+    C = crf_check_classes(num_classes)
+    img = _crf_images(images_u8)
+    N, H, W, _ = img.shape
+    n = H * W
+    if not (isinstance(masks_i32, torch.Tensor) and masks_i32.is_cuda and masks_i32.dtype == torch.int32
+            and tuple(masks_i32.shape) == (N, H, W)):
+        raise Dl3pError('dense_crf takes (N, H, W) int32 masks on the HIP device that match the images')
+    if int(iterations) < 0:
+        raise ValueError('iterations must not be negative (got %r)' % (iterations,))
+    mask = masks_i32.contiguous()
+    dev = img.device
+    key = (dev.index, N, H, W)
+    ws = _crf_ws.get(key)
+    if ws is None:
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = _crf_ws[key] = {'census': torch.zeros((N, 2), dtype=torch.int32, device=dev),
+                             'q': torch.empty((N, n, CRF_LP), **f32), 'fg': torch.empty((N, n, CRF_LP), **f32),
+                             'fb': torch.empty((N, n, CRF_LP), **f32), 'tmp': torch.empty((N, n, CRF_LP), **f32),
+                             'ng': torch.empty(n, **f32), 'nb': torch.empty((N, n), **f32)}
+    L, st = lib(), _stream()
+    q, fg, fb = ws['q'], ws['fg'], ws['fb']
+    sx, sy = _sxy(sxy_gaussian)
+    gt = float(gt_prob)
+    out = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    L.crf_unary(_p(mask), _p(ws['census']), _p(q), CRF_LP, gt, N, n, C, st)
+    if int(iterations) == 0:
+        L.crf_update(_p(mask), _p(ws['census']), None, None, None, None, 0.0, 0.0, gt, None, CRF_LP, _p(out), N, n, C, st)
+    else:
+        L.crf_gauss_norm(_p(ws['ng']), H, W, sx, sy, st)
+        L.crf_bilateral_message(_p(img), None, 0, None, None, 0, _p(ws['nb']), N, H, W, float(sxy_bilateral), float(srgb), st)
+    for t in range(int(iterations)):
+        last = t == int(iterations) - 1
+        L.crf_gauss_message(_p(q), CRF_LP, _p(ws['ng']), _p(ws['tmp']), _p(fg), CRF_LP, N, H, W, sx, sy, st)
+        L.crf_bilateral_message(_p(img), _p(q), CRF_LP, _p(ws['nb']), _p(fb), CRF_LP, None, N, H, W, float(sxy_bilateral),
+                                float(srgb), st)
+        L.crf_update(_p(mask), _p(ws['census']), _p(fg), _p(ws['ng']), _p(fb), _p(ws['nb']), float(compat_gaussian),
+                     float(compat_bilateral), gt, _p(q) if (not last or want_q) else None, CRF_LP, _p(out) if last else None, N, n, C,
+                     st)
+    if want_q:
+        return out, q.view(N, H, W, CRF_LP)[..., :C].clone()
+    return out
+
+
+def mask_confusion(pred_mask, labels, num_classes, confusion=None):
+    """confusion[label, mask] += 1 over every pixel whose label is a class: pred_mask int32 and labels float32 of the same number of
+    pixels, confusion (C, C) int64 on the device (made here when None) -> confusion"""
+    if confusion is None:
+        confusion = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=pred_mask.device)
+    assert pred_mask.dtype == torch.int32 and labels.dtype == torch.float32 and pred_mask.numel() == labels.numel()
+    lib().mask_confusion(_p(pred_mask.contiguous()), _p(labels.contiguous()), _p(confusion), pred_mask.numel(), int(num_classes),
+                         _stream())
+    return confusion
+
+
+def denormalize_u8(x):
+    """the reference's denormalize_image on the device: float32 in [-1, 1] -> uint8, (x * 127.5 + 127.5) truncated"""
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    lib().denormalize_u8(_p(x), _p(out), x.numel(), _stream())
+    return out
