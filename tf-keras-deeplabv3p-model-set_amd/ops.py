@@ -1557,6 +1557,11 @@ def dense_crf(images_u8, masks_i32, num_classes, *, iterations=5, gt_prob=0.7, s
     """fully connected CRF refinement of hard class masks (the reference's deeplabv3p/postprocess_np.py crf_postprocess with
     zero_unsure=False, every filter exact instead of pydensecrf's lattice): images (N,H,W,3) uint8 and masks (N,H,W) int32 on the
     device -> refined masks (N,H,W) int32, and Q (N,H,W,C) float32 with want_q.  A mask with a single class comes back unchanged.
+    A class id outside [0, C) (an ignore label such as 255, say) is neither refused nor a class: it is not counted among the present
+    classes and carries no evidence -- the pixel's unary term is that of "another class" for every present class -- while the pixel
+    takes part in the messages like any other and leaves with a class in [0, C).  An image with fewer than two present classes comes
+    back unchanged, such ids included.  iterations=0 returns the argmax of the unary term: a pixel's own class where
+    gt_prob > 1 / n_labels, the lowest present id for an id outside [0, C).
     Runs on the current stream and does not synchronise; the buffers are kept per (device, N, H, W)"""
     C = crf_check_classes(num_classes)
     img = _crf_images(images_u8)
