@@ -1044,6 +1044,45 @@ int dl3p_topk_threshold(const float* loss_map, size_t P, double top_k_percent, i
                         int step_bias, int first_histogram_ready, void* workspace, void* record, void* stream);
 int dl3p_mining_weights(const float* loss_map, const float* base, const void* record, float* weights, size_t P, void* stream);
 
+/* ---------------------------------------------------------------- region losses (csrc/region_loss.hip)
+ * Soft Dice, soft Jaccard and Tversky on the softmax of the bilinearly upsampled logits, alone or added to one of the per-pixel losses.
+ * With p_i the probabilities dl3p_upsample_softmax_loss forms at full-resolution pixel i and the valid pixels those it counts (label
+ * in [0, C) and not ignore_index != 0), per class c over the valid pixels of the batch: I_c = sum p_ic [y_i == c], P_c = sum p_ic,
+ * Y_c = |{y_i == c}|, D_c = (1 - alpha - beta) I_c + alpha P_c + beta Y_c + smooth, T_c = (I_c + smooth) / D_c; S = {c : Y_c > 0};
+ * R = (1 / |S|) sum over S of (1 - T_c), 0 when S is empty.  alpha = beta = 1/2: Dice; alpha = beta = 1: Jaccard.  Three stages,
+ * fp32 with 64-bit offsets, P = N*H*W < 2^31, no floating-point atomics, no (N,H,W,C) probability tensor, results bitwise repeatable.
+ * Cpad = C rounded up to 4.
+ * dl3p_region_sums: one pass over the full-resolution pixels (z, ldz, labels, (h, w) -> (H, W) as for dl3p_upsample_softmax_loss,
+ * h <= H and w <= W) that leaves *rows_out partial rows in workspace (dl3p_region_workspace(C) bytes on the device, 16-byte aligned,
+ * room for DL3P_MAX_STAT_ROWS rows; no need to clear it).  A row is [3][Cpad] words: float I_c, float P_c, int32 Y_c of one workgroup's
+ * pixels, summed thread -> wave -> workgroup in a fixed order.  The number of rows depends on N*H*W only.
+ * dl3p_region_finalize: one workgroup adds the rows in fixed order in float64 and writes record (4 + 3 Cpad words on the device,
+ * 16-byte aligned) = {float region_weight * R, int32 |S|, 0, 0, float T[Cpad], float A[Cpad], float B[Cpad]}:
+ * A_c = region_weight a_c / |S|, B_c = region_weight b_c / |S| with a_c = 1 / D_c - (1 - alpha - beta) (I_c + smooth) / D_c^2 and
+ * b_c = alpha (I_c + smooth) / D_c^2 for c in S; outside S (and for c >= C) A_c = B_c = 0 and T_c = NaN.  So
+ * d (region_weight R) / d p_ic = B_c - [y_i == c] A_c at a valid pixel.
+ * dl3p_region_head_grad: the head of the compiled loss base_weight * base + region_weight * R.  base_kind: DL3P_LOSS_CE,
+ * DL3P_LOSS_WEIGHTED_CE (class_weights[C] required), DL3P_LOSS_FOCAL, or DL3P_REGION_BASE_NONE; inv_count, class_weights, focal_gamma,
+ * focal_alpha and pixel_weights act on the base term only and mean what they mean to dl3p_upsample_softmax_loss.  With
+ * g_c = B_c - [y_i == c] A_c from record, dlogits_big[i][c] = base_weight w_i f inv_count (p_ic - [y_i == c]) + p_ic (g_c - sum_k p_ik g_k)
+ * at a valid pixel, 0 at any other, 0 in the pad channels [C, ld_big) (ld_big >= C; rows with ld_big % 4 == 0 and ld_big <= 32 leave as
+ * whole 16-byte vectors and need a 16-byte aligned base and ldz >= ld_big).  loss_partials[*rows_out] (room for DL3P_MAX_STAT_ROWS):
+ * the base term's partial sums times base_weight and inv_count, and one last row that holds region_weight * R, so dl3p_reduce_rows
+ * over them is the compiled loss.  dlogits_big == NULL: the value only.  dl3p_resize_bilinear_bwd carries dlogits_big to the logits.
+ * DL3P_EINVAL before any launch: C outside [1, 256], ldz % 4 != 0 or ldz < Cpad, h > H or w > W, a size < 1, P >= 2^31, a null or
+ * misaligned z / workspace / record, null labels / loss_partials / rows_out, a bad base kind (weighted CE without class_weights), alpha or
+ * beta <= 0, smooth < 0, region_weight <= 0, base_weight < 0, any of them not finite, rows outside [1, DL3P_MAX_STAT_ROWS]. */
+enum { DL3P_REGION_BASE_NONE = -1 };
+size_t dl3p_region_workspace(int C);
+int dl3p_region_sums(const float* z, int ldz, const float* labels, int ignore_index, void* workspace, int* rows_out, int N, int h,
+                     int w, int C, int H, int W, void* stream);
+int dl3p_region_finalize(const void* workspace, int rows, int C, float alpha, float beta, float smooth, float region_weight,
+                         void* record, void* stream);
+int dl3p_region_head_grad(const float* z, int ldz, const float* labels, int ignore_index, float inv_count, int base_kind,
+                          const float* class_weights, float focal_gamma, float focal_alpha, const float* pixel_weights,
+                          float base_weight, const void* record, float* dlogits_big, int ld_big, float* loss_partials, int* rows_out,
+                          int N, int h, int w, int C, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- dense CRF post-processing (csrc/crf.hip)
  * Mean-field inference of the fully connected CRF (unary from a hard class mask, a Gaussian and a bilateral Potts kernel, symmetric
  * normalisation), every message pass the exact sum out_i = sum_j k(f_i, f_j) V_j over ALL pixels j of the image, j == i included.

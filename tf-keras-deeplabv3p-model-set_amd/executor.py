@@ -21,6 +21,7 @@ import torch
 from ._lib import lib
 from .exec_options import GHOST_ON_BY_DEFAULT, ExecOptions       # noqa: F401  (every DL3P_* switch of this file: exec_options.ROWS)
 from .graph import ACT_NONE, ACT_RELU
+from .losses import REGION_NEAREST_TEXT
 
 MAX_ROWS = 2048
 # the module shapes (K, c) the fused ghost forward was built for, and from how many pixels per batch (N*H*W): the `ghost` rows
@@ -467,8 +468,13 @@ class BackwardTrace:
 class Executor:
     def __init__(self, graph, head, store, batch, training, num_classes, ignore_index=255, dist=None,
                  seed=1234, momentum=0.9, loss=('ce',), optimizer=None, sample_weighted=False, class_counts=False,
-                 averaging=None, clip=None, mining=None):
+                 averaging=None, clip=None, mining=None, region=None):
         self.g, self.head, self.store = graph, head, store
+        # region loss: None | (alpha, beta, smooth, region_weight, base_weight, has_base) (losses.loss_spec): the compiled loss is
+        # base_weight * `loss` + region_weight * R over this executor's batch (csrc/region_loss.hip); without a base
+        # `loss` is not evaluated
+        self.region = region
+        self._region_host, self._region_evt, self._region_posted = None, None, None
         # hard-example mining: None | (top_k_percent_pixels, hard_example_mining_step) (losses.mining_spec): the loss and its gradient
         # come from the k highest-loss pixels of this executor's batch (csrc/mining.hip)
         self.mining = mining
@@ -672,12 +678,19 @@ class Executor:
             self.mining_weights = torch.zeros(N * H * W, **self.f32)
             self.mining_ws = torch.zeros(L.mining_workspace() // 4, dtype=torch.int32, device=self.dev)
             self.mining_record = torch.zeros(8, dtype=torch.int32, device=self.dev)
+        # region loss: the partial rows of the sums and the record {rho R, |S|, 0, 0, T, A, B} the gradient launch reads
+        self.region_ws = self.region_record = None
+        if self.region is not None and zt is not None:
+            if getattr(g, 'head_upsample', 'bilinear') == 'nearest':
+                raise ValueError(REGION_NEAREST_TEXT)
+            self.region_ws = torch.zeros(L.region_workspace(self.C) // 4, **self.f32)
+            self.region_record = torch.zeros(4 + 3 * ((self.C + 3) // 4 * 4), **self.f32)
         # per-image class counts for the Jaccard training metric (deeplabv3p/metrics.py:29-46), refreshed every step
         self.metric_counts = (torch.zeros(N * 3 * self.C, dtype=torch.int32, device=self.dev).view(N, 3, self.C)
                               if (self.training and self.want_class_counts) else None)
         want = self.opts.fused_head       # the fused training heads, plain cross-entropy only: the `fused_head` row of exec_options.py
         plain = bool(self.training and self.loss_kind == 0 and not self.sample_weighted and self.mining is None and
-                     self.class_weights is None and zt is not None and zt.requires_grad)
+                     self.region is None and self.class_weights is None and zt is not None and zt.requires_grad)
         # (the logits and their gradient stay fp32 under the bf16 policy -- _is_f32 -- so the separable head serves it too; the padded
         # classes of the gradient buffer are never written by anyone and keep the zeros they were allocated with)
         # UpSampling2D((r, r)) in front of the softmax (Fast-SCNN): the dl3p_nearest_* head, one softmax per logit pixel.  Its
@@ -1194,6 +1207,23 @@ class Executor:
         launch(L.mining_weights, self.loss_map.data_ptr(), base, self.mining_record.data_ptr(), self.mining_weights.data_ptr(), P)
         return self.mining_weights.data_ptr()
 
+    def _region_stages(self, launch, pixel_w, dlogits):
+        """sums -> finalize -> gradient (csrc/region_loss.hip); launch(fn, *args) issues one of them.  dlogits None: the value only.
+        -> the rows of self.loss_partials (the base term's partial sums and rho R) whose dl3p_reduce_rows is the compiled loss"""
+        L, zt = self.L, self.head.tensor
+        alpha, beta, smooth, rho, base_weight, has_base = self.region
+        rrows, rows = ctypes.c_int(0), ctypes.c_int(0)
+        launch(L.region_sums, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0), self.region_ws.data_ptr(),
+               ctypes.byref(rrows), self.N, zt.H, zt.W, self.C, self.H, self.W)
+        launch(L.region_finalize, self.region_ws.data_ptr(), rrows.value, self.C, alpha, beta, smooth, rho,
+               self.region_record.data_ptr())
+        launch(L.region_head_grad, self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
+               1.0 / float(self.N * self.H * self.W), self.loss_kind if has_base else -1,
+               None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma, self.loss_alpha, pixel_w,
+               base_weight, self.region_record.data_ptr(), dlogits, self.cpad, self.loss_partials.data_ptr(), ctypes.byref(rows),
+               self.N, zt.H, zt.W, self.C, self.H, self.W)
+        return rows
+
     def _head_forward(self, P):
         """pred_resize + softmax (+ loss and its gradient when training)"""
         L, N, train = self.L, self.N, self.training
@@ -1218,7 +1248,10 @@ class Executor:
                 P.k(L.nearest_class_counts, self.tptr(zt), zt.ld, self.labels.data_ptr(), self.metric_counts.data_ptr(), N, zt.H,
                     zt.W, self.C, self.H, self.W)
             return
-        if train and self.fused_head:
+        if train and self.region is not None:
+            rows = self._region_stages(P.k, pixel_w, self.dlogits_big.data_ptr())
+            P.k(L.reduce_rows, self.loss_partials.data_ptr(), rows.value, 1, self.loss.data_ptr(), 0)
+        elif train and self.fused_head:
             # loss + d loss / d (conv_upsample output) in one launch; the full-resolution gradient is never written
             ws = (self.head_ws.data_ptr(), self.head_wsb) if self.fused_head_rows else ()
             P.k(L.head_train_rows if self.fused_head_rows else L.head_train, self.tptr(zt), zt.ld, self.labels.data_ptr(),
@@ -2344,6 +2377,28 @@ class Executor:
         self._mine_evt[i].record()
         self._mine_posted = i
 
+    def _post_region(self):
+        """start the copy of this step's region record to pinned host memory behind the plans, like _post_mining"""
+        if self._region_host is None:
+            self._region_host = [torch.zeros(self.region_record.numel(), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            self._region_evt = [torch.cuda.Event(), torch.cuda.Event()]
+            self._region_k = 0
+        i = self._region_k & 1
+        self._region_k += 1
+        self._region_host[i].copy_(self.region_record, non_blocking=True)
+        self._region_evt[i].record()
+        self._region_posted = i
+
+    def last_region(self):
+        """{'loss': region_weight * R, 'present': |S|, 'score': T_c per class, NaN outside S} of the last train_step (None: no region
+        loss, or no step yet); waits for its copy only"""
+        i = self._region_posted
+        if i is None:
+            return None
+        self._region_evt[i].synchronize()
+        h = self._region_host[i].numpy()
+        return {'loss': float(h[0]), 'present': int(h[1:2].view(np.int32)[0]), 'score': h[4:4 + self.C].copy()}
+
     def last_mining(self):
         """{'k', 'threshold', 'kept', 'nonzero'} of the last train_step (None: no mining, or no step yet); waits for its copy only"""
         i = self._mine_posted
@@ -2457,6 +2512,8 @@ class Executor:
             self._post_grad_norm()
         if self.mining is not None:
             self._post_mining()
+        if self.region is not None:
+            self._post_region()
         if self.store.Sb is not None:
             self.store.sb_partial = self
 
@@ -2503,7 +2560,9 @@ class Executor:
         rows = ctypes.c_int(0)
         # (mining: the validation loss is the mean over the kept set too, at the step count the optimiser stands at)
         pixel_w = None if self.mining is None else self._mining_stages(lambda fn, *a: fn(*a, st), 0)
-        if self.nearest_head:
+        if self.region is not None:
+            rows = self._region_stages(lambda fn, *a: fn(*a, st), pixel_w, None)
+        elif self.nearest_head:
             L.nearest_head_train(self.tptr(zt), zt.ld, self.labels.data_ptr(), int(self.ignore_index or 0),
                                  1.0 / float(self.N * self.H * self.W), self.loss_kind,
                                  None if self.class_weights is None else self.class_weights.data_ptr(), self.loss_gamma,

@@ -53,6 +53,73 @@ class SparseSoftmaxFocalLoss(object):
         self.__name__ = 'sparse_softmax_focal_loss'
 
 
+def _finite_number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+        raise ValueError('%s must be a finite number, got %r' % (name, v))
+    return float(v)
+
+
+# what compile() answers where a region loss meets the nearest-upsampling head (Fast-SCNN)
+REGION_NEAREST_TEXT = ('region losses (SparseTverskyLoss, SparseDiceLoss, SparseJaccardLoss) run behind the bilinear head only: the '
+                      'nearest-upsampling head has no region kernels (a dl3p_nearest_region_sums and a dl3p_nearest_region_head_grad '
+                      'next to dl3p_nearest_head_train are not built)')
+
+
+class SparseTverskyLoss(object):
+    """A region (overlap) loss on the model's softmax, alone or added to one of the per-pixel losses (DESIGN section 7,
+    csrc/region_loss.hip).  Per class over the valid pixels of the batch: I = sum p [y == c], P = sum p, Y = |y == c|,
+    T = (I + smooth) / ((1 - alpha - beta) I + alpha P + beta Y + smooth), i.e. (I + s) / (I + alpha FP + beta FN + s); the loss is
+    the mean of 1 - T over the classes present in the labels (0 when none is).  alpha weighs false positives, beta false negatives.
+    The compiled loss is base_weight * base + region_weight * that mean; base: None or a SparseCategoricalCrossEntropy,
+    WeightedSparseCategoricalCrossEntropy or SparseSoftmaxFocalLoss with everything it carries (class weights, focal parameters,
+    mining); sample weights act on the base term only."""
+
+    def __init__(self, alpha=0.5, beta=0.5, smooth=1.0, ignore_index=None, from_logits=False, *, base=None, base_weight=1.0,
+                 region_weight=1.0):
+        if from_logits:
+            raise ValueError('the model emits probabilities (Softmax pred_mask); from_logits=%r is not supported' % (from_logits,))
+        self.alpha, self.beta = _finite_number('alpha', alpha), _finite_number('beta', beta)
+        self.smooth = _finite_number('smooth', smooth)
+        self.region_weight, self.base_weight = _finite_number('region_weight', region_weight), _finite_number('base_weight', base_weight)
+        if self.alpha <= 0.0 or self.beta <= 0.0:
+            raise ValueError('alpha and beta must be > 0, got alpha=%r beta=%r' % (alpha, beta))
+        if self.smooth < 0.0:
+            raise ValueError('smooth must be >= 0, got %r' % (smooth,))
+        if self.region_weight <= 0.0:
+            raise ValueError('region_weight must be > 0, got %r' % (region_weight,))
+        if self.base_weight < 0.0:
+            raise ValueError('base_weight must be >= 0, got %r' % (base_weight,))
+        if base is not None and type(base) not in (SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy,
+                                                   SparseSoftmaxFocalLoss):
+            raise ValueError('base must be None or one of the per-pixel losses (SparseCategoricalCrossEntropy, '
+                             'WeightedSparseCategoricalCrossEntropy, SparseSoftmaxFocalLoss), got %r' % (base,))
+        if base is not None and base.ignore_index != ignore_index:
+            raise ValueError('base.ignore_index=%r differs from ignore_index=%r: one label rule serves both terms'
+                             % (base.ignore_index, ignore_index))
+        self.base = base
+        self.ignore_index = ignore_index
+        self.from_logits = from_logits
+        self.__name__ = 'sparse_tversky_loss'
+
+
+class SparseDiceLoss(SparseTverskyLoss):
+    """soft Dice: Tversky with alpha = beta = 1/2, T = (2 I + 2 s) / (P + Y + 2 s)"""
+
+    def __init__(self, smooth=1.0, ignore_index=None, from_logits=False, *, base=None, base_weight=1.0, region_weight=1.0):
+        super().__init__(0.5, 0.5, smooth, ignore_index, from_logits, base=base, base_weight=base_weight,
+                         region_weight=region_weight)
+        self.__name__ = 'sparse_dice_loss'
+
+
+class SparseJaccardLoss(SparseTverskyLoss):
+    """soft Jaccard, the differentiable form of the IoU: Tversky with alpha = beta = 1, T = (I + s) / (P + Y - I + s)"""
+
+    def __init__(self, smooth=1.0, ignore_index=None, from_logits=False, *, base=None, base_weight=1.0, region_weight=1.0):
+        super().__init__(1.0, 1.0, smooth, ignore_index, from_logits, base=base, base_weight=base_weight,
+                         region_weight=region_weight)
+        self.__name__ = 'sparse_jaccard_loss'
+
+
 def Jaccard(y_true=None, y_pred=None):
     """deeplabv3p/metrics.py:29-46, train.py:140 `metrics = {'pred_mask': Jaccard}`: a marker for compile(metrics=...);
     the counts come from dl3p_class_counts on the device and jaccard_from_counts evaluates them"""
@@ -83,7 +150,11 @@ def _wants_jaccard(metrics):
 
 
 def loss_spec(loss):
-    """-> ('ce',) | ('weighted', weights) | ('focal', gamma, alpha): what the head kernel (and the oracle) need"""
+    """-> ('ce',) | ('weighted', weights) | ('focal', gamma, alpha): what the head kernel (and the oracle) need;
+    a region loss: ('region', alpha, beta, smooth, region_weight, base_weight, the base's spec or None)"""
+    if isinstance(loss, SparseTverskyLoss):
+        return ('region', loss.alpha, loss.beta, loss.smooth, loss.region_weight, loss.base_weight,
+                None if loss.base is None else loss_spec(loss.base))
     if isinstance(loss, WeightedSparseCategoricalCrossEntropy):
         return ('weighted', loss.weights)
     if isinstance(loss, SparseSoftmaxFocalLoss):
@@ -93,7 +164,10 @@ def loss_spec(loss):
 
 def mining_spec(loss):
     """-> None (every pixel trains: top_k_percent_pixels == 1.0) | (p, M): the loss and its gradient come from the
-    k = int((r p + 1 - r) P) highest-loss pixels of the batch, r = min(1, step / M) (csrc/mining.hip)"""
+    k = int((r p + 1 - r) P) highest-loss pixels of the batch, r = min(1, step / M) (DESIGN section 7, csrc/mining.hip);
+    a region loss mines what its base mines"""
+    if isinstance(loss, SparseTverskyLoss):
+        return None if loss.base is None else mining_spec(loss.base)
     p = float(getattr(loss, 'top_k_percent_pixels', 1.0))
     if p == 1.0:
         return None

@@ -18,7 +18,7 @@ from .mobilenetv2 import Deeplabv3pMobileNetV2, Deeplabv3pLiteMobileNetV2
 from .optimizers import (_clip_args, SGD, Adam, RMSprop, _AveragedOptimizer, MovingAverage, SWA, Lookahead,  # noqa: F401
                          get_averaged_optimizer, get_optimizer)
 from .losses import (SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy, SparseSoftmaxFocalLoss, Jaccard,  # noqa: F401
-                     jaccard_from_counts, _wants_jaccard, loss_spec, mining_spec, miou_from_confusion)
+                     SparseTverskyLoss, SparseDiceLoss, SparseJaccardLoss, REGION_NEAREST_TEXT, jaccard_from_counts, _wants_jaccard, loss_spec, mining_spec, miou_from_confusion)
 from .feed import DistContext, StagedBatch, BatchFeeder, LateScalar  # noqa: F401
 from .callbacks import EvalCallBack, AverageModelCheckpoint  # noqa: F401
 
@@ -185,6 +185,8 @@ class DeeplabModel:
         # Keras keeps the slot variables and `iterations` on the optimizer OBJECT: compiling again with the same object
         # (train.py:224 after unfreezing) continues its schedule and momentum, a new object (train.py:190-224 builds one
         # for the second stage) starts its schedule at step 0 with fresh slots
+        if isinstance(loss, SparseTverskyLoss) and getattr(self.graph, 'head_upsample', 'bilinear') == 'nearest':
+            raise ValueError(REGION_NEAREST_TEXT)
         same_optimizer = optimizer is not None and optimizer is self.optimizer
         self.optimizer = optimizer or SGD(0.01)
         self.loss = loss or SparseCategoricalCrossEntropy(ignore_index=255)
@@ -290,6 +292,15 @@ class DeeplabModel:
         ex = self._last_train_ex
         return ex.last_mining() if ex is not None else None
 
+    @property
+    def last_region(self):
+        """the region term of the last training step: {'loss': region_weight * R, 'present': the number of classes present in the
+        batch's labels, 'score': the soft overlap T_c per class, NaN for a class that is not present}; None while no region loss
+        (SparseTverskyLoss, SparseDiceLoss, SparseJaccardLoss) is compiled or before the first step.  Follows its step to the host
+        asynchronously, like last_mining."""
+        ex = self._last_train_ex
+        return ex.last_region() if ex is not None else None
+
     def _executor(self, batch, training):
         avg = self._avg_spec() if training else None
         clip = self._clip_spec() if training else None
@@ -302,11 +313,15 @@ class DeeplabModel:
             ignore = self.loss.ignore_index if self.loss is not None else 255
             opt = self.optimizer.spec() if self.optimizer is not None else ('sgd', 0.9)
             rank = self.dist.rank if self.dist is not None else 0
+            spec, region = loss_spec(self.loss), None
+            if spec[0] == 'region':      # the executor takes the base's spec as its per-pixel loss, and the region parameters beside it
+                region, spec = spec[1:6] + (spec[6] is not None,), (spec[6] or ('ce',))
             self._exec[key] = Executor(self.graph, self.head, store, batch, training, self.num_classes,
                                        ignore_index=ignore, dist=self.dist if training else None,
-                                       seed=self.seed + 7919 * rank, loss=loss_spec(self.loss), optimizer=opt,
+                                       seed=self.seed + 7919 * rank, loss=spec, optimizer=opt,
                                        sample_weighted=self.sample_weight_mode == 'temporal',
-                                       class_counts=self._jaccard, averaging=avg, clip=clip, mining=mining_spec(self.loss))
+                                       class_counts=self._jaccard, averaging=avg, clip=clip, mining=mining_spec(self.loss),
+                                       region=region)
         return self._exec[key]
 
     def train_on_batch(self, x, y, sample_weight=None, return_tensor=False):

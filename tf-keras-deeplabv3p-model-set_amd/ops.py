@@ -1488,6 +1488,96 @@ def mining_weights(loss_map, record, base=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------- region losses (csrc/region_loss.hip)
+REGION_BASE_NONE = -1
+REGION_RECORD_HEAD = 4          # {rho R, |S|, 0, 0} in front of T[Cpad], A[Cpad], B[Cpad]
+
+
+def region_workspace(C, device):
+    """room for the partial rows [3][Cpad] of region_sums (never needs clearing)"""
+    return torch.empty(lib().region_workspace(int(C)) // 4, dtype=torch.float32, device=device)
+
+
+def region_record(C, device):
+    """the device record region_finalize fills: 4 + 3 Cpad words"""
+    return torch.zeros(REGION_RECORD_HEAD + 3 * ((int(C) + 3) // 4 * 4), dtype=torch.float32, device=device)
+
+
+def region_sums(z, C, H, W, labels, ignore_index=255, workspace=None):
+    """z (N,h,w,Cpad) logits, labels [N*H*W] -> (workspace, rows): rows partial rows [3][Cpad] = float I_c, float P_c, int32 Y_c over
+    the valid pixels of one workgroup each (I_c = sum p_ic [y_i == c], P_c = sum p_ic, Y_c = |y_i == c|)"""
+    N, h, w, _ = z.shape
+    zp, ldz = _pl(z)
+    if workspace is None:
+        workspace = region_workspace(C, z.device)
+    rows = ctypes.c_int(0)
+    lib().region_sums(zp, ldz, _p(labels), int(ignore_index or 0), _p(workspace), ctypes.byref(rows), N, h, w, C, H, W, _stream())
+    return workspace, rows.value
+
+
+def region_finalize(workspace, rows, C, alpha, beta, smooth=1.0, region_weight=1.0, record=None):
+    """-> record, float32 [4 + 3 Cpad] on the device: {region_weight * R, |S| (int32 bits), 0, 0, T[Cpad], A[Cpad], B[Cpad]}"""
+    if record is None:
+        record = region_record(C, workspace.device)
+    lib().region_finalize(_p(workspace), int(rows), C, float(alpha), float(beta), float(smooth), float(region_weight), _p(record),
+                          _stream())
+    return record
+
+
+def region_head_grad(z, C, H, W, labels, record, ignore_index=255, base=None, base_weight=1.0, pixel_weights=None, want_grad=True,
+                     out=None, ld_big=None):
+    """the head of base_weight * base + region_weight * R -> (loss [1], dlogits (N,H,W,ld_big) or None); base: None | ('ce',) |
+    ('weighted', weight tensor [C]) | ('focal', gamma, alpha); record: region_finalize's"""
+    N, h, w, _ = z.shape
+    dev = z.device
+    zp, ldz = _pl(z)
+    if ld_big is None:
+        ld_big = out.shape[-1] if out is not None else (C + 3) // 4 * 4
+    if want_grad and out is None:
+        out = torch.empty((N, H, W, ld_big), dtype=torch.float32, device=dev)
+    kind = REGION_BASE_NONE if base is None else {'ce': 0, 'weighted': 1, 'focal': 2}[base[0]]
+    cw = base[1] if kind == 1 else None
+    gamma, alpha = (float(base[1]), float(base[2])) if kind == 2 else (0.0, 0.0)
+    partial = torch.zeros(MAX_STAT_ROWS, dtype=torch.float32, device=dev)
+    rows = ctypes.c_int(0)
+    lib().region_head_grad(zp, ldz, _p(labels), int(ignore_index or 0), 1.0 / float(N * H * W), kind, _p(cw), gamma, alpha,
+                           _p(pixel_weights), float(base_weight), _p(record), _p(out) if want_grad else None, ld_big, _p(partial),
+                           ctypes.byref(rows), N, h, w, C, H, W, _stream())
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    lib().reduce_rows(_p(partial), rows.value, 1, _p(total), 0, _stream())
+    return total, (out if want_grad else None)
+
+
+def region_loss(z, C, H, W, labels, alpha=0.5, beta=0.5, smooth=1.0, region_weight=1.0, ignore_index=255, base=None, base_weight=1.0,
+                pixel_weights=None, want_grad=True, ld_big=None):
+    """sums -> finalize -> head gradient in one call -> dict(loss [1] tensor: base_weight * base + region_weight * R; sums: (3, C)
+    float64 on the host, the partial rows added up, [I, P, Y]; record: the device record; dlogits (N,H,W,ld_big) or None)"""
+    ws, rows = region_sums(z, C, H, W, labels, ignore_index)
+    record = region_finalize(ws, rows, C, alpha, beta, smooth, region_weight)
+    loss, dlogits = region_head_grad(z, C, H, W, labels, record, ignore_index, base, base_weight, pixel_weights, want_grad,
+                                     ld_big=ld_big)
+    return dict(loss=loss, sums=region_partial_sums(ws, rows, C), record=record, dlogits=dlogits)
+
+
+def region_partial_sums(workspace, rows, C):
+    """the partial rows of region_sums added up in float64 on the host -> (3, C): I_c, P_c, Y_c (inspection; the device's own sum is
+    region_finalize's)"""
+    import numpy as np
+    cp = (C + 3) // 4 * 4
+    part = workspace[:rows * 3 * cp].cpu().numpy().reshape(rows, 3, cp)
+    sums = part[:, :2].astype(np.float64).sum(axis=0)
+    counts = np.ascontiguousarray(part[:, 2]).view(np.int32).astype(np.float64).sum(axis=0)
+    return np.concatenate([sums, counts[None]], axis=0)[:, :C]
+
+
+def region_record_fields(record, C):
+    """the record on the host -> dict(loss, present, score [C], A [C], B [C])"""
+    cp = (C + 3) // 4 * 4
+    h = record.cpu().numpy()
+    return dict(loss=float(h[0]), present=int(h[1:2].view('int32')[0]), score=h[4:4 + C].copy(), A=h[4 + cp:4 + cp + C].copy(),
+                B=h[4 + 2 * cp:4 + 2 * cp + C].copy())
+
+
 # ---- dense CRF post-processing (csrc/crf.hip, DESIGN section 7) ----------------------------------------------------------------
 CRF_LP = 32                 # columns of a class-vector row: the column count of v_mfma_f32_32x32x2_f32
 CRF_MAX_CLASSES = 32
