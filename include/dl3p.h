@@ -331,6 +331,15 @@ int dl3p_conv2d_gemm_bwd_weight(const float* x, int ldx, const float* in_scale, 
  * dl3p_conv2d_gemm_bwd_weight_workspace accounts for it. */
 int dl3p_conv2d_gemm_sb_supported(int role, int M, int K, int N);
 int dl3p_conv2d_gemm_sb_pays(int role, int M, int K, int N);
+/* What the dense-conv entry points WOULD launch for the GEMM (M, K, N) as above, without launching it: the planning functions
+ * the launches themselves call.  role 0 / 1: dl3p_conv2d_gemm_fwd without / with statistics, 2: dl3p_conv2d_gemm_bwd_data;
+ * 5 / 6 / 7: their _sb twins (out6 = {-1} where dl3p_conv2d_gemm_sb_supported(role - 5, ...) says no).  out6 = {nt (16-column
+ * tiles per workgroup), mi (tile rows / 64), grid x (= the statistic rows written), grid y, M tiles, 0}: a workgroup walks
+ * ceil((M tiles - x) / grid x) M tiles.  role 4: dl3p_conv2d_gemm_bwd_weight[_slabs] with the workspace
+ * dl3p_conv2d_gemm_bwd_weight_workspace asks for: out6 = {form (0 tiled fp32, 4 split-bf16), tile index (tiled: 0 64x64, 1 128x64,
+ * 2 64x128, 3 128x128 of k x n; split: as "split_wgrad_tile"), k tiles x n tiles, slabs, rows of M per slab (the last one
+ * shorter), 0}. */
+int dl3p_conv2d_gemm_plan_query(int role, int M, int K, int N, int* out6);
 int dl3p_conv2d_gemm_fwd_sb(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
                             const void* wsp, int pitch, const float* bias, float* y, int ldy, float* stat_partials,
                             int* rows_out, int N, int H, int W, int Cin, int Cout, int k, int stride, int rate, int pad_t,

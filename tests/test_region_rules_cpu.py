@@ -112,7 +112,12 @@ BAD = [dict(from_logits=True), dict(alpha=0.0), dict(alpha=-1.0), dict(beta=0.0)
        dict(base='ce'), dict(base=object()), dict(alpha='0.5')]
 
 
-@pytest.mark.parametrize('kw', BAD, ids=[str(sorted(k.items())) for k in BAD])
+def _bad_id(kw):
+    """the case's arguments as its id; a bare object() by name, not by its address (which differs from run to run)"""
+    return str(sorted((n, 'object()' if type(v) is object else v) for n, v in kw.items()))
+
+
+@pytest.mark.parametrize('kw', BAD, ids=[_bad_id(k) for k in BAD])
 def test_bad_arguments_are_refused_with_their_value(kw):
     pkg = load_pkg()
     with pytest.raises(ValueError) as e:

@@ -1219,6 +1219,16 @@ static void conv_gather_dgrad(GemmParams* p, int H, int W, int Cout, int k, int 
   p->g_cmagic = (uint32_t)((1ull << 32) / (unsigned)Cout) + 1u;
   p->g_kwmagic = 65536 / k + 1;
 }
+// the plan of the fp32 implicit GEMMs (forward: N = Cout over output pixels; data gradient: N = Cin over input pixels): the
+// heuristics only -- the measured table and the pinned tiles belong to the pointwise launches.  What the launches below and
+// dl3p_conv2d_gemm_plan_query both take.
+static GemmPlan plan_conv_gemm(int M, int N) {
+  GemmPlan pl = {};
+  pl.form = FORM_TILED;
+  pl.nt = pick_nt(N, M);
+  gemm_grid(&pl, M, N);
+  return pl;
+}
 // the gathered operand [N][H][W][ld] and the GEMM-side operand [M][ldm] both stay under 4 GiB
 static bool conv_fits_4g(int N, int H, int W, int ld, int M, int ldm) {
   return fits_4g((unsigned long long)N * H * W, {ld}) && fits_4g(M, {ldm});
@@ -1239,9 +1249,7 @@ extern "C" int dl3p_conv2d_gemm_fwd(const float* x, int ldx, const float* in_sca
   fill_fwd(&p, x, ldx, in_scale, in_shift, in_act, bias, y, ldy, stat_partials, M, K, Cout);
   p.B = wt; p.ldb = K;
   conv_gather_fwd(&p, H, W, Cin, k, stride, rate, pad_t, pad_l, Ho, Wo);
-  GemmPlan pl = {};
-  pl.nt = pick_nt(Cout, M);
-  gemm_grid(&pl, M, Cout);
+  const GemmPlan pl = plan_conv_gemm(M, Cout);
   p.num_m_tiles = pl.m_tiles;
   if (rows_out) *rows_out = pl.gx;
   if (stat_partials) launch_gemm<false, true, false, true>(p, pl.nt, pl.mi, dim3(pl.gx, pl.gy), (hipStream_t)stream);
@@ -1275,9 +1283,7 @@ extern "C" int dl3p_conv2d_gemm_bwd_data(const float* dy, int lddy, const float*
   fill_dgrad(&p, dy, lddy, gx, ldgx, accumulate, M, Cin, K);
   p.B = wd; p.ldb = K;
   conv_gather_dgrad(&p, H, W, Cout, k, stride, rate, pad_t, pad_l, Ho, Wo);
-  GemmPlan pl = {};
-  pl.nt = pick_nt(Cin, M);
-  gemm_grid(&pl, M, Cin);
+  const GemmPlan pl = plan_conv_gemm(M, Cin);
   p.num_m_tiles = pl.m_tiles;
   launch_gemm<false, false, false, true>(p, pl.nt, pl.mi, dim3(pl.gx, pl.gy), (hipStream_t)stream);
   DL3P_CHECK_LAUNCH(fn);
@@ -1365,11 +1371,22 @@ extern "C" int dl3p_conv2d_gemm_bwd_data_sb(const float* dy, int lddy, const voi
   return DL3P_OK;
 }
 
-extern "C" size_t dl3p_conv2d_gemm_bwd_weight_workspace(int N, int Ho, int Wo, int Cin, int Cout, int k) {
-  if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || k <= 0) return 0;
-  const size_t a = wgrad_workspace_slabs(N * Ho * Wo, k * k * Cin, Cout, true) * k * k * Cin * Cout;
+static size_t conv_wgrad_workspace_bytes(int M, int K, int Cout) {
+  const size_t a = wgrad_workspace_slabs(M, K, Cout, true) * K * Cout;
   const size_t b = (size_t)512 * Cout;   // slabs; bias column-sum partial rows
   return (a > b ? a : b) * sizeof(float);
+}
+extern "C" size_t dl3p_conv2d_gemm_bwd_weight_workspace(int N, int Ho, int Wo, int Cin, int Cout, int k) {
+  if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || k <= 0) return 0;
+  return conv_wgrad_workspace_bytes(N * Ho * Wo, k * k * Cin, Cout);
+}
+
+// the plan of the gathered weight gradient for a workspace of workspace_bytes (launch and dl3p_conv2d_gemm_plan_query)
+static WgradPlan plan_conv_wgrad(int M, int K, int Cout, size_t workspace_bytes) {
+  WgradTraits t;
+  t.max_slabs = workspace_bytes / ((size_t)K * Cout * 4);
+  t.gathered = true;
+  return plan_wgrad(M, K, Cout, t);
 }
 
 static int conv2d_gemm_bwd_weight_impl(const float* x, int ldx, const float* in_scale, const float* in_shift, int in_act,
@@ -1388,10 +1405,7 @@ static int conv2d_gemm_bwd_weight_impl(const float* x, int ldx, const float* in_
     dl3p_set_error("%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
     return DL3P_EWORKSPACE;
   }
-  WgradTraits t;
-  t.max_slabs = workspace_bytes / ((size_t)K * Cout * 4);
-  t.gathered = true;
-  const WgradPlan pl = plan_wgrad(M, K, Cout, t);
+  const WgradPlan pl = plan_conv_wgrad(M, K, Cout, workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
   if (pl.form == WGRAD_SPLIT) {
     const int geo[10] = {Ho, Wo, H, W, Cin, k, stride, -pad_t, -pad_l, rate};
@@ -1428,6 +1442,29 @@ extern "C" int dl3p_conv2d_gemm_bwd_weight_slabs(const float* x, int ldx, const 
   DL3P_CHECK_ARG(rows_out != nullptr, "dl3p_conv2d_gemm_bwd_weight_slabs: rows_out is required");
   return conv2d_gemm_bwd_weight_impl(x, ldx, in_scale, in_shift, in_act, dy, lddy, nullptr, nullptr, workspace, workspace_bytes,
                                      N, H, W, Cin, Cout, k, stride, rate, pad_t, pad_l, Ho, Wo, rows_out, stream);
+}
+
+// the plans of the dense-conv entry points above, reported instead of launched (include/dl3p.h).  (M, K, N) is the GEMM as launched;
+// the weight gradient is planned for the workspace dl3p_conv2d_gemm_bwd_weight_workspace asks for
+extern "C" int dl3p_conv2d_gemm_plan_query(int role, int M, int K, int N, int* out6) {
+  DL3P_CHECK_ARG(out6 && role >= 0 && role <= 7 && role != 3 && M > 0 && K > 0 && N > 0, "dl3p_conv2d_gemm_plan_query: bad arguments");
+  for (int i = 0; i < 6; ++i) out6[i] = 0;
+  if (role == 4) {
+    const WgradPlan pl = plan_conv_wgrad(M, K, N, conv_wgrad_workspace_bytes(M, K, N));
+    out6[0] = pl.form;
+    if (pl.form == WGRAD_SPLIT) {
+      out6[1] = pl.sb_nw == 16 ? 4 : (pl.kf == 2 ? 0 : 1) + (pl.sb_nw == 8 ? 0 : 2);
+      out6[2] = pl.sb_ktiles * pl.sb_ntiles; out6[3] = pl.slabs; out6[4] = pl.mrows;
+    } else {
+      out6[1] = (pl.kw == 2 ? 1 : 0) + (pl.nw == 8 ? 2 : 0);
+      out6[2] = pl.ktiles * pl.ntiles; out6[3] = pl.slabs; out6[4] = pl.mchunk;
+    }
+    return DL3P_OK;
+  }
+  if (role >= 5 && !dl3p_conv2d_gemm_sb_supported(role - 5, M, K, N)) { out6[0] = -1; return DL3P_OK; }
+  const GemmPlan pl = role >= 5 ? plan_gemm_sb_ga(M, N) : plan_conv_gemm(M, N);
+  out6[0] = pl.nt; out6[1] = pl.mi; out6[2] = pl.gx; out6[3] = pl.gy; out6[4] = pl.m_tiles;
+  return DL3P_OK;
 }
 
 // ====================================================================================== plan query (include/dl3p.h)

@@ -721,6 +721,13 @@ def conv2d_gemm_supported(Cin, Cout, k, stride):
     return bool(lib().conv2d_gemm_supported(Cin, Cout, k, stride))
 
 
+def conv2d_gemm_plan_query(role, M, K, N):
+    """the plan of a dense-conv implicit GEMM without launching it (include/dl3p.h: dl3p_conv2d_gemm_plan_query) -> the six ints"""
+    out = (ctypes.c_int * 6)()
+    lib().conv2d_gemm_plan_query(role, M, K, N, out)
+    return tuple(out)
+
+
 def conv2d_gemm_fwd(x, w, stride=1, rate=1, padding='same', in_scale=None, in_shift=None, in_act=ACT_NONE, bias=None,
                     partials=None, out=None):
     """dense conv as an implicit GEMM (no im2col matrix): x (N,H,W,Cin), w (k,k,Cin,Cout) -> y (N,Ho,Wo,Cout) [, rows];
